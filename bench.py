@@ -4,7 +4,10 @@
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 launched with
 ``torch.distributed.run --nproc-per-node N`` (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env).
 W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier + synchronize on both
-sides, elapsed = MAX over ranks, rank 0 prints ONE JSON line.
+sides, elapsed = MAX over ranks, rank 0 prints ONE JSON line.  Such a plain run does only that
+(set up, warm up, time, print); ``--full`` adds the measurements the headline figure does not
+need (at N > 1 the extra pure-TP layout).  ``--dump-outputs DIR`` writes the last timed step's
+results (loss, gradients, updated weights) as ``DIR/<name>.npy`` for build-to-build comparison.
 
 Config (BASELINE.json metric "tokens/sec (whole node), GPT-2-small TP at 1/2/4/8 MI355X"):
 GPT-2 small shape in the reference block (d=768, 12 layers, 12 heads, SwiGLU ffn 2048,
@@ -77,6 +80,13 @@ def parse():
     ap.add_argument("--fp8", action="store_true",
                     help="fp8 (e4m3 / e5m2) forward and data-gradient GEMMs on hipBLASLt fp8 kernels (ops/fp8.py); "
                          "NOT the bf16 headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (its loss, the "
+                         "gradients it left in .grad and the weights after its optimizer step; a fixed seeded "
+                         "sample of the large tensors) as DIR/<name>.npy in float32")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: at N > 1 with a TP x DP headline layout, the "
+                         "extra pure-TP (tp = N) measurement next to it (a plain run times the headline only)")
     return ap.parse_args()
 
 
@@ -94,10 +104,38 @@ def resolve_tp(tp: str, model: str, world: int) -> int:
     return t
 
 
-def measure(a, tp: int, world: int, dev, first: bool):
+# --dump-outputs: at most this many float32 elements in all (48 MiB of data plus the .npy headers)
+DUMP_BUDGET_ELEMS = 12 * 2 ** 20
+
+
+def dump_outputs(dirname: str, loss, model, world: int):
+    """Write what the last timed step handed its caller as ``<name>.npy`` (float32): the loss,
+    every parameter's gradient as the backward left it and every weight after the optimizer
+    step.  A tensor larger than its share of DUMP_BUDGET_ELEMS is written as a sample at fixed
+    seeded flat indices (same arguments: same indices), so two builds compare element for
+    element.  One rank writes into ``dirname``; several write ``dirname/rank<r>`` each."""
+    import numpy as np
+    d = dirname if world == 1 else os.path.join(dirname, f"rank{dist.get_rank()}")
+    os.makedirs(d, exist_ok=True)
+    named = [("loss", loss.detach().reshape(1))]
+    for n, p in model.named_parameters():
+        if p.grad is not None:
+            named.append(("grad." + n, p.grad.detach()))
+        named.append(("weight." + n, p.detach()))
+    cap = DUMP_BUDGET_ELEMS // len(named)
+    g = torch.Generator().manual_seed(20250101)
+    for name, t in named:
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            flat = flat[torch.randint(0, flat.numel(), (cap,), generator=g).to(flat.device)]
+        np.save(os.path.join(d, name + ".npy"), flat.float().cpu().numpy())
+
+
+def measure(a, tp: int, world: int, dev, first: bool, dump: bool = False):
     """Build the model on a (dp = world / tp) x tp grid, run the warmup (with the engine trial
     at TP > 1) and EXACTLY ``a.steps`` timed steps bracketed by barrier + synchronize on both
-    sides.  Returns the layout's numbers (elapsed = max over ranks)."""
+    sides.  Returns the layout's numbers (elapsed = max over ranks).  ``dump``: this is the
+    headline layout, whose last step ``--dump-outputs`` writes out."""
     from distributed_pytorch_from_scratch_amd.models import get_preset, Transformer
     from distributed_pytorch_from_scratch_amd.ops.optim import FusedAdam
     from distributed_pytorch_from_scratch_amd.engine import TrainStep
@@ -272,6 +310,8 @@ def measure(a, tp: int, world: int, dev, first: bool):
         peak_mem_gb=round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2) if dev.type == "cuda" else None,
         trial={f"{'sp' if k[0] else 'nosp'}/c{k[1]}": round(1000 * v, 2) for k, v in trial.items()} or None,
         graph=graphed)
+    if dump and a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss, model, world)
     del model, opt, pool
     if a.impl == "ours":
         del step
@@ -301,7 +341,7 @@ def main():
 
     failed = False
     try:
-        head = measure(a, tp, world, dev, first=True)
+        head = measure(a, tp, world, dev, first=True, dump=True)
     except Exception as e:   # noqa: BLE001
         # The TP x DP layout failed on every rank alike (an exception, not a hang: a hang ends
         # at the process-group timeout).  Pure data parallelism is measured for the record, but
@@ -314,7 +354,7 @@ def main():
               file=sys.stderr, flush=True)
         from distributed_pytorch_from_scratch_amd.parallel import tp_comm
         tp_comm.reset()
-        head = measure(a, 1, world, dev, first=False)
+        head = measure(a, 1, world, dev, first=False, dump=True)
         head["headline_error"] = {"parallelism": f"tp{tp}dp{world // tp}", "error": err}
         a.pure_tp = False
         failed = True
@@ -327,13 +367,13 @@ def main():
         out["mfu_vs_2.5pf_dense_bf16"] = None
         out["config"]["parallelism"] = head["headline_error"]["parallelism"]
     # The reference trains with tp_size == world_size (process_manager.py:13-15, recipe.sh TP 1 /
-    # 2 / 4): at N > 1 the pure-TP layout is measured as well and reported next to the headline
+    # 2 / 4): with --full at N > 1 the pure-TP layout is measured as well and reported next to the headline
     # layout (same contract: W warmup + K timed steps, max over ranks), each with its label.
     # That layout must never cost the headline: it runs after the headline's numbers are final,
     # any exception becomes tp_pure = {"error": ...}, and a per-rank timer bounds it (a hung
     # collective: rank 0 prints the headline line with tp_pure = {"error": "timeout"} and every
     # rank exits 0 before the process-group watchdog or the driver's lease fires).
-    if world > 1 and tp != world and a.pure_tp:
+    if world > 1 and tp != world and a.pure_tp and a.full:
         import threading
         lock = threading.Lock()
         done = []

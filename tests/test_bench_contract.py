@@ -69,29 +69,70 @@ def test_bench_tp_dp_layout():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", "4", "--tp", "2", "--model", "plumbing", "--steps", "2", "--warmup", "1", "--seq-len", "64",
-           "--batch-per-gpu", "2"]
+           "--batch-per-gpu", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     (d,) = _json_lines(r.stdout)
     assert d["config"]["parallelism"] in ("tp2dp2", "tp2dp2+sp") and d["config"]["global_batch"] == 8
     assert d["n_gpus"] == 4 and d["value"] > 0
-    # the pure-TP layout (the reference's tp_size == world_size) is measured and labelled too
+    # --full: the pure-TP layout (the reference's tp_size == world_size) is measured and labelled too
     labels = [L["parallelism"].split("+")[0] for L in d["layouts"]]
     assert labels == ["tp2dp2", "tp4"], labels
     assert d["tp_pure"]["parallelism"].startswith("tp4") and d["tp_pure"]["value"] > 0
     assert d["tp_pure"]["ms_per_step"] > 0
 
 
+def test_bench_plain_run_times_the_headline_only():
+    """Without --full the TP x DP headline is the only layout measured: no pure-TP extra."""
+    from dist_helpers import _free_port
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
+           "--gpus", "4", "--tp", "2", "--model", "plumbing", "--steps", "2", "--warmup", "1", "--seq-len", "64",
+           "--batch-per-gpu", "2"]
+    r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    (d,) = _json_lines(r.stdout)
+    assert REQUIRED <= d.keys() and d["value"] > 0 and d["ms_per_step"] > 0
+    assert [L["parallelism"].split("+")[0] for L in d["layouts"]] == ["tp2dp2"]
+    assert d["tp_pure"] is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR writes the last timed step's loss, gradients and updated weights as
+    float32 .npy files (64 MB at the most); the same arguments give the same inputs, so two runs
+    of one build on the CPU agree exactly."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--model", "plumbing", "--steps", "3", "--warmup", "1",
+               "--seq-len", "64", "--batch-per-gpu", "2", "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        (d,) = _json_lines(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / name))
+        assert "loss.npy" in files and all(f.endswith(".npy") for f in files)
+        assert any(f.startswith("grad.") for f in files) and any(f.startswith("weight.") for f in files)
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 * 10 ** 6
+        arrs = {f: np.load(tmp_path / name / f) for f in files}
+        assert all(v.dtype == np.float32 and v.size > 0 and np.isfinite(v).all() for v in arrs.values())
+        assert abs(float(arrs["loss.npy"][0]) - d["final_loss"]) < 1e-3
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 @pytest.mark.parametrize("inject", ["raise:0", "hang:3"])
 def test_bench_pure_tp_failure_keeps_headline(inject):
     """A failure (exception on one rank) or a hang (one rank never arrives) in the extra pure-TP
-    layout still yields exactly one JSON line with the headline numbers, tp_pure = {error}, and
+    layout of a ``--full`` run still yields exactly one JSON line with the headline numbers, tp_pure = {error}, and
     exit status 0 on every rank."""
     from dist_helpers import _free_port
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", "4", "--tp", "2", "--model", "plumbing", "--steps", "2", "--warmup", "1", "--seq-len", "64",
-           "--batch-per-gpu", "2", "--pure-tp-budget-s", "25"]
+           "--batch-per-gpu", "2", "--full", "--pure-tp-budget-s", "25"]
     env = dict(_env(), DPFS_BENCH_INJECT=inject)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

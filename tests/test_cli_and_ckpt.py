@@ -160,10 +160,8 @@ def test_data_pipeline(tmp_path):
 
 def test_reference_tokenizer_fixture_if_present():
     """The reference ships tokenizer/tokenizer.json (BPE, vocab 1024, <BOS>/<EOS>/<UNK> = 0/1/2);
-    our tokenizer tooling must load it unchanged (read-only fixture)."""
-    path = "/root/reference/tokenizer/tokenizer.json"
-    if not os.path.exists(path):
-        pytest.skip("reference fixture not mounted")
+    our tokenizer tooling must load it unchanged (stored copy: tests/golden/reference_tokenizer.json)."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_tokenizer.json")
     tokenizers = pytest.importorskip("tokenizers")
     tok = tokenizers.Tokenizer.from_file(path)
     assert tok.get_vocab_size() == 1024

@@ -1,7 +1,7 @@
 """(Named to run last in the GPU suite: the longest and most box-sensitive tests.)
 
 Rehearsal of the driver's multi-GPU bench (SCALE: N = 2, 4, 8 back to back) on one MI355X:
-``bench.py --gpus N`` under ``torch.distributed.run`` with N ranks sharing the GPU (gloo
+``bench.py --gpus N --full`` under ``torch.distributed.run`` with N ranks sharing the GPU (gloo
 bootstrap; RCCL refuses two ranks on one device), the ``auto`` TP transport decision enabled on
 gloo (``DPFS_TP_COMM_AUTO_ANY_BACKEND=1``: xGMI kernels -- two-shot and one-shot -- and, at
 TP 2 with other pairs, the relayed exchange are built, validated and timed per size class), and
@@ -44,7 +44,7 @@ def test_bench_n_ranks_on_one_gpu(n, layouts):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", str(n), "--layers", "1", "--seq-len", "128", "--batch-per-gpu", "2", "--steps", "2",
-           "--warmup", "2", "--pure-tp-budget-s", "120"]
+           "--warmup", "2", "--full", "--pure-tp-budget-s", "120"]
     # the ranks' output goes to a log file as it comes (gpurun_out/ on the GPU box: a run that
     # prints nothing for minutes is taken to be hung), read back afterwards
     logdir = os.path.join(ROOT, "gpurun_out") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else None
