@@ -134,6 +134,9 @@ void dpfs_gemv16(const void*, long long, const void*, long long, const float*, v
                  hipStream_t);
 void dpfs_rope_append(void*, long long, const int64_t*, const float*, void*, void*, const int*, int, int, int, int,
                       hipStream_t);
+// kernels/sample.hip
+void dpfs_sample_logits(const void*, int, long long, int, int, int, float, int, double, unsigned long long,
+                        const int64_t*, const float*, int64_t*, int*, float*, float*, hipStream_t);
 // comm/xgmi.hip
 const char* dpfs_xgmi_last_error();
 long long dpfs_xgmi_handle_bytes();
@@ -1366,6 +1369,40 @@ void step_advance(torch::Tensor len, torch::Tensor pos) {
   dpfs_step_advance(len.data_ptr<int>(), pos.data_ptr<int64_t>(), (int)pos.numel(), stream());
 }
 
+// Temperature / top-k / top-p sampling of one token per row (kernels/sample.hip): logits
+// [B, >= vocab] bf16 / fp32 with unit column stride, columns >= vocab are padding.  top_k 0 or
+// >= vocab and top_p 1 are off.  The uniform of row b is Philox4x32-10(key seed, counter
+// (pos[b], b, 0)) unless `u` [B] supplies it (tests).  Returns (ids int64, kept int32, thresh
+// fp32, u fp32), each [B].  No host synchronisation: graph-capturable.
+py::tuple sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
+                        int64_t seed, torch::Tensor pos, c10::optional<torch::Tensor> u) {
+  check_rowmajor(logits, "logits");
+  const int dt = dcode(logits);
+  const int64_t B = logits.size(0), ld = logits.stride(0), vec = dt == 1 ? 8 : 4;
+  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab < (1LL << 31) && (B <= 1 || ld >= logits.size(1)),
+              "sample_logits: 1 <= vocab <= ld, got vocab ", vocab, " for rows of ", logits.size(1));
+  TORCH_CHECK(temperature > 0.0, "sample_logits: temperature must be > 0, got ", temperature);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0, got ", top_k);
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == B,
+              "sample_logits: pos must be contiguous int64 [B]");
+  const float* up = opt_f32(u, B, "u");
+  const at::DeviceGuard g(logits.device());
+  auto ids = torch::empty({B}, pos.options());
+  auto kept = torch::empty({B}, pos.options().dtype(torch::kInt32));
+  auto thresh = torch::empty({B}, pos.options().dtype(torch::kFloat32));
+  auto uo = torch::empty({B}, pos.options().dtype(torch::kFloat32));
+  // 16-byte row loads need aligned rows whose last vector lies inside the row
+  const int64_t esz = dt == 1 ? 2 : 4;
+  const bool vec_ok = reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 && (B <= 1 || ld * esz % 16 == 0) &&
+                      (vocab + vec - 1) / vec * vec <= logits.size(1);
+  const int k = (int)std::min<int64_t>(top_k, vocab);
+  dpfs_sample_logits(logits.data_ptr(), dt, ld, (int)B, (int)vocab, vec_ok ? 1 : 0, (float)(1.0 / temperature), k, top_p,
+                     (unsigned long long)seed, pos.data_ptr<int64_t>(), up, ids.data_ptr<int64_t>(),
+                     kept.data_ptr<int>(), thresh.data_ptr<float>(), uo.data_ptr<float>(), stream());
+  return py::make_tuple(ids, kept, thresh, uo);
+}
+
 // ------------------------------------------------------------- xGMI collectives (comm/) --
 void* xgmi_ptr(int64_t h) {
   TORCH_CHECK(h != 0, "xgmi: null communicator");
@@ -1698,6 +1735,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("len"));
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seed"), py::arg("pos"), py::arg("u") = py::none());
   m.def("xgmi_create", &xgmi_create, "allocate IPC buffers: -> (handle, ipc handle bytes)");
   m.def("xgmi_open", &xgmi_open, "map every peer's buffers (rank-ordered concatenated handle bytes)");
   m.def("xgmi_run", &xgmi_run, py::arg("h"), py::arg("op"), py::arg("x"), py::arg("out"), py::arg("world"),

@@ -10,7 +10,8 @@ the validation loss (batch 1, bf16) is written to ``{ckpt_dir}/val/tprank-{r}_va
 Fixed reference bugs: the decode loads ``ckpt_paths[-1]`` (the reference
 indexes the last *character* of a path string, ``test.py:124``), and the embedding no longer
 mutates the token buffer, so TP>1 decoding is correct.  Extensions: ``--synthetic_prompts``
-(token-id prompts when no tokenizer file is available) and the vocab-parallel loss.
+(token-id prompts when no tokenizer file is available), the vocab-parallel loss, and sampled
+decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily).
 """
 from __future__ import annotations
 
@@ -65,6 +66,10 @@ def get_test_args(argv=None):
     g.add_argument("--max_decode_len", type=int, default=128)
     g.add_argument("--synthetic_prompts", action="store_true")
     g.add_argument("--no_kv_cache", action="store_true", help="re-run the full prefix per token (reference)")
+    g.add_argument("--temperature", type=float, default=0.0, help="0: greedy (reference); > 0: sample")
+    g.add_argument("--top_k", type=int, default=0, help="sample from the k largest logits (0: off)")
+    g.add_argument("--top_p", type=float, default=1.0, help="sample from the top-p nucleus (1: off)")
+    g.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling draws")
     g = p.add_argument_group("other")
     g.add_argument("--random_seed", type=int, default=0)
     g.add_argument("--device", type=str, default=None)
@@ -87,16 +92,22 @@ def calc_loss(model: Transformer, dataloader, dev) -> float:
 
 
 @torch.inference_mode()
-def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True):
+def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True,
+                  temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
-    (``models/generation.py``); ``False`` re-runs the whole prefix per token like the reference."""
+    (``models/generation.py``); ``False`` re-runs the whole prefix per token like the reference.
+    ``temperature`` > 0 samples instead (``top_k`` / ``top_p`` / ``seed`` as in ``generate``);
+    sampling runs in the KV-cached decode step only."""
+    if temperature != 0 and not kv_cache:
+        raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
     if kv_cache:
         from .models.generation import generate
         n0 = 1 + len(prompt_ids)
         tokens = torch.tensor([bos] + list(prompt_ids), dtype=torch.long, device=dev).view(1, -1)
-        out = generate(model, tokens, max_new_tokens=max(1, max_len + 1 - n0), eos_id=eos)[0]
+        out = generate(model, tokens, max_new_tokens=max(1, max_len + 1 - n0), eos_id=eos, temperature=temperature,
+                       top_k=top_k, top_p=top_p, seed=seed)[0]
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
             out = out[:-1]
@@ -150,12 +161,13 @@ def test(rank, args):
 
     ck.load_model(model, paths[-1])
     ds = loader.dataset
+    sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.sample_seed)
     decoded = []
     if args.synthetic_prompts or not args.tokenizer_path:
         for i in range(4):
             g = torch.Generator().manual_seed(i)
             ids = torch.randint(3, margs.vocab_size, (8,), generator=g).tolist()
-            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache)
+            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
             assert out[:len(ids)] == ids
             decoded.append((str(ids), str(out[len(ids):])))
     else:
@@ -165,7 +177,7 @@ def test(rank, args):
         for t in PROMPTS:
             t = t.strip()
             ids = tok.encode(t).ids
-            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache)
+            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
             text = tok.decode(out).strip()
             decoded.append((t, text[len(t):] if text.startswith(t) else text))
     with open(save_path, "a") as fp:
@@ -181,6 +193,8 @@ def test(rank, args):
 
 def main(argv=None):
     args = get_test_args(argv)
+    if args.no_kv_cache and args.temperature != 0:
+        raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)
     mp.spawn(test, args=(args,), nprocs=args.tp_size, join=True)

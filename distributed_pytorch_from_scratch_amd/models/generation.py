@@ -16,6 +16,10 @@ for the local head shard:
   are all-reduced and the vocab-sharded logits all-gathered, so every rank picks the same
   token).  ``DPFS_DECODE_GRAPH=0`` forces the eager step.
 
+The token choice is ``argmax`` (greedy, the default) or, with ``temperature > 0``, one
+``sample_logits`` launch (csrc/kernels/sample.hip: temperature, top-k, top-p, a stateless
+Philox draw keyed on (seed, row, position)) inside the same captured step.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -31,6 +35,8 @@ import torch
 # decode steps captured per HIP graph replay (the host reads the tokens / checks EOS once per
 # replay; profiles/r2_decode_bench.jsonl)
 _GRAPH_STEPS = 8
+# captured graphs kept per session (greedy: 2; sampling: 2 per (temperature, top_k, top_p, seed))
+_MAX_GRAPHS = 16
 
 from ..ops import gemm_select as GS
 from ..ops.dispatch import K, shadow
@@ -110,13 +116,28 @@ def logits_step(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     return logits[..., : model.vocab_size].float()
 
 
-def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache):
+def _pick(model, logits: torch.Tensor, pos: torch.Tensor, sample):
+    """Next ids (B,) and the fp32 (B, vocab) logits from the gathered (B, padded vocab) logits:
+    ``argmax`` without ``sample``, else one ``sample_logits`` launch on the gathered rows with
+    ``sample`` = (temperature, top_k, top_p, seed) and the step's device positions (every TP
+    rank holds the same rows, seed and positions, so the ranks agree)."""
+    if sample is None:
+        logits = logits[..., : model.vocab_size].float()
+        return logits.argmax(-1), logits
+    temperature, top_k, top_p, seed = sample
+    nxt = K(logits).sample_logits(logits, model.vocab_size, temperature, top_k, top_p, seed, pos)[0]
+    return nxt, logits[..., : model.vocab_size].float()
+
+
+def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sample=None):
     """One token per sequence (``ids`` (B, 1), ``pos`` (B,) int64 = cache.len_t) against the
     cache; advances ``cache.len_t`` and ``pos`` on the device.  Returns (next ids (B,),
-    logits (B, vocab) fp32).  Touches no host state: graph-capturable."""
+    logits (B, vocab) fp32); the ids are the ``argmax``, or with ``sample`` = (temperature,
+    top_k, top_p, seed) a draw keyed on (seed, row, ``pos``).  Touches no host state:
+    graph-capturable."""
     from .fused_engine import _Layer
     if model.args.norm != "rmsnorm":
-        return _decode_step_modules(model, ids, pos, cache)
+        return _decode_step_modules(model, ids, pos, cache, sample)
     B = ids.size(0)
     dev = ids.device
     dt = model.act_dtype(dev)
@@ -156,13 +177,12 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache):
         tp_comm.all_reduce(pend, async_op=False)
     _, hfin, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, model.norm.scale, model.norm.eps)
     logits = proj(hfin, W(model.lm_head.weight), model.lm_head.bias)
-    logits = comm_ops.Gather.apply(logits, model.lm_head.sizes)[..., : model.vocab_size].float()
-    nxt = logits.argmax(-1)
+    nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
     K(pos).step_advance(cache.len_t, pos)
     return nxt, logits
 
 
-def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache):
+def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sample=None):
     """decode_step through the nn.Module layers (any norm type, e.g. the LayerNorm variant)."""
     B = ids.size(0)
     dev = ids.device
@@ -180,8 +200,7 @@ def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVC
         x = x + attn.wo(k_.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(hd)))
         x = x + layer.ffn(layer.norm2(x))
     logits = model._lm_head_local(model.norm(x))
-    logits = comm_ops.Gather.apply(logits, model.lm_head.sizes)[..., : model.vocab_size].float()
-    nxt = logits.argmax(-1)
+    nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
     K(pos).step_advance(cache.len_t, pos)
     return nxt, logits
 
@@ -190,9 +209,12 @@ class DecodeGraph:
     """``nsteps`` decode steps captured as one HIP graph (static ids / pos / output buffers):
     step s writes its next ids into ``outs[s]`` and feeds them to step s + 1 on the device, so
     the host reads the tokens back (and checks EOS) once per replay instead of once per token
-    (that round trip, ~90 us, was idle GPU time in every step)."""
+    (that round trip, ~90 us, was idle GPU time in every step).  ``sample`` = (temperature,
+    top_k, top_p, seed) captures sampling steps: the settings are launch arguments of the
+    captured ``sample_logits`` nodes (a session keys its graphs on them), and the draw reads the
+    device positions, so a replay at any position draws what the eager step draws there."""
 
-    def __init__(self, model, cache: KVCache, B: int, nsteps: int = 1):
+    def __init__(self, model, cache: KVCache, B: int, nsteps: int = 1, sample=None):
         dev = cache.len_t.device
         self.cache = cache
         self.nsteps = nsteps
@@ -206,14 +228,14 @@ class DecodeGraph:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             self.pos.copy_(cache.len_t.long().expand(B))
-            decode_step(model, self.ids, self.pos, cache)
+            decode_step(model, self.ids, self.pos, cache, sample)
         torch.cuda.current_stream().wait_stream(s)
         cache.len_t.copy_(saved)
         _graph_rng_state_normal(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             for i in range(nsteps):
-                nxt, self.logits = decode_step(model, self.ids, self.pos, cache)
+                nxt, self.logits = decode_step(model, self.ids, self.pos, cache, sample)
                 self.outs[i].copy_(nxt)
                 if i + 1 < nsteps:
                     self.ids.copy_(nxt.view(-1, 1))
@@ -289,10 +311,21 @@ def clear_sessions():
 
 @torch.inference_mode()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
-             max_len: Optional[int] = None) -> List[List[int]]:
-    """Greedy decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
+             max_len: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+             seed: int = 0) -> List[List[int]]:
+    """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
-    output) or when the total length reaches ``max_len`` (default: model maxlen)."""
+    output) or when the total length reaches ``max_len`` (default: model maxlen).
+
+    ``temperature`` 0 decodes greedily.  ``temperature`` > 0 samples every token with
+    ``sample_logits``: softmax(logits / temperature) cut to the ``top_k`` largest logits (0:
+    off) and then to the ``top_p`` nucleus (1: off), ties at either cutoff kept whole.  The draw
+    for the token that follows position t of row b depends only on (``seed``, b, t), so the same
+    call returns the same tokens on the graph and the eager path and on every TP rank."""
+    if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
+        raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
+                         f"{temperature}, {top_k}, {top_p}")
+    sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
     B, T0 = prompt.shape
     dev = prompt.device
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
@@ -301,7 +334,12 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     done = [False] * B
     if max_new_tokens <= 0 or T0 >= t_max:
         return out
-    nxt = logits_step(model, prompt, cache).argmax(-1)
+    logits = logits_step(model, prompt, cache)
+    if sample is None:
+        nxt = logits.argmax(-1)
+    else:   # the first token follows position T0 - 1
+        pos0 = torch.full((B,), T0 - 1, dtype=torch.int64, device=dev)
+        nxt = K(logits).sample_logits(logits, model.vocab_size, *sample, pos0)[0]
     cache.sync_device_len()
     pos = torch.full((B,), cache.len, dtype=torch.int64, device=dev)
     chunk = _GRAPH_STEPS
@@ -323,9 +361,13 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         if _use_graph(dev):
             # S steps per replay while S more tokens are wanted and the cache has room for them
             S = chunk if (max_new_tokens - n_gen >= chunk and cache.len + chunk <= t_max) else 1
-            g = graphs.get(S)
+            gkey = S if sample is None else (S, sample)
+            g = graphs.get(gkey)
             if g is None:
-                g = graphs[S] = DecodeGraph(model, cache, B, S)
+                if sample is not None and len(graphs) >= _MAX_GRAPHS:
+                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != sample]:
+                        del graphs[k]     # sampling graphs of earlier settings; greedy ones stay
+                g = graphs[gkey] = DecodeGraph(model, cache, B, S, sample)
             g.pos.fill_(cache.len)
             outs = g.step(nxt)
             rows = outs.tolist()
@@ -335,7 +377,7 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
                 if emit(row):
                     return out
         else:
-            nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache)
+            nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
             cache.len += 1
             if emit(nxt.tolist()):
                 return out

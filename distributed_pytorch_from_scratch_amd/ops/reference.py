@@ -255,6 +255,80 @@ def step_advance(len: torch.Tensor, pos: torch.Tensor) -> None:
     pos.fill_(int(len.reshape(-1)[0]))
 
 
+# ----------------------------------------------------------------------- sampling ----
+
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., Random123) on Python integers: ``counter`` 4 and ``key`` 2
+    32-bit words -> 4 output words.  Counter 0 with key 0 gives word 0 = 0x6627E8D5."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed: int, pos: int, row: int) -> float:
+    """The sampling uniform of (seed, position, row): key (seed lo32, seed hi32), counter
+    (pos lo32, pos hi32, row, 0), u = (x0 >> 8) * 2^-24 in [0, 1) (exact in fp32)."""
+    s, p = int(seed) & 0xFFFFFFFFFFFFFFFF, int(pos) & 0xFFFFFFFFFFFFFFFF
+    x0 = philox4x32_10((p & _M32, p >> 32, row, 0), (s & _M32, s >> 32))[0]
+    return (x0 >> 8) * 2.0 ** -24
+
+
+def sample_logits(logits: torch.Tensor, vocab: int, temperature: float, top_k: int, top_p: float, seed: int,
+                  pos: torch.Tensor, u: Optional[torch.Tensor] = None):
+    """Temperature / top-k / top-p sampling of one token per row of ``logits`` (B, >= vocab);
+    columns >= vocab are padding.  z = fp32(logit) * fp32(1/T) (one fp32 multiply), weights
+    exp(z - max z) and every mass in fp64.  Top-k keeps ``logit >= v_k`` (the k-th largest;
+    ties all kept; 0 or >= vocab: off); top-p then keeps, of the survivors, ``logit >= t*`` with
+    t* the largest value present whose upper set holds a share >= p of the survivors' mass
+    (ties kept whole; 1: off).  The token is the smallest kept index j whose inclusive kept
+    mass C_j (vocabulary order) exceeds u * C_last, u = ``sample_uniform(seed, pos[b], b)``
+    unless ``u`` (B,) supplies it.  Returns (ids int64, kept int32, thresh fp32 -- the final
+    cutoff as a raw logit, the row minimum with both filters off --, u fp32), each (B,)."""
+    assert temperature > 0 and 0 < top_p <= 1 and top_k >= 0 and 1 <= vocab <= logits.size(1)
+    B, dev = logits.size(0), logits.device
+    x = logits[:, :vocab].float()
+    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32, device=dev)
+    z = (x * inv_t).double()
+    w = torch.exp(z - z.max(-1, keepdim=True).values)
+    thresh = x.min(-1).values
+    if 0 < top_k < vocab:
+        thresh = x.topk(top_k, dim=-1).values[:, -1]
+    keep = x >= thresh[:, None]
+    if top_p < 1:
+        xs, order = x.sort(dim=-1, descending=True, stable=True)
+        ks = keep.gather(-1, order)
+        cum = (w.gather(-1, order) * ks).cumsum(-1)
+        total = cum[:, -1:]
+        # S(value) = the cumulative mass at the end of the value's run of ties
+        last = torch.ones_like(ks)
+        last[:, :-1] = xs[:, :-1] != xs[:, 1:]
+        run_end = torch.where(last, cum, torch.full_like(cum, float("inf"))).flip(-1).cummin(-1).values.flip(-1)
+        ok = ks & (run_end >= top_p * total)
+        first = ok.to(torch.int8).argmax(-1, keepdim=True)      # descending order: the largest value
+        thresh = xs.gather(-1, first)[:, 0]
+        keep = keep & (x >= thresh[:, None])
+    if u is None:
+        u = torch.tensor([sample_uniform(seed, p, b) for b, p in enumerate(pos.tolist())], dtype=torch.float32,
+                         device=dev)
+    u = u.to(device=dev, dtype=torch.float32)
+    wk = w * keep
+    C = wk.cumsum(-1)
+    hit = keep & (C > u.double()[:, None] * C[:, -1:])
+    ids = hit.to(torch.int8).argmax(-1)
+    # rounding left no C_j above u * M: the last kept index with a non-zero weight
+    idx = torch.arange(vocab, device=dev).expand(B, vocab)
+    fallback = torch.where(wk > 0, idx, torch.zeros_like(idx)).max(-1).values
+    ids = torch.where(hit.any(-1), ids, fallback)
+    return ids, keep.sum(-1).to(torch.int32), thresh, u
+
+
 def _rot_bthd(x: torch.Tensor, positions: torch.Tensor, table: torch.Tensor, inverse: bool) -> torch.Tensor:
     """Rotate-half RoPE of an fp32 (B, T, H, hd) tensor; ``positions`` is flat [B*T]."""
     B, T, H, hd = x.shape

@@ -2,9 +2,13 @@
 reference's full recompute per token (test.py:144-150), one GPU.
 
     python tools/decode_bench.py [--model gpt2-small] [--batch 1 8] [--prompt 128] [--new 256]
+                                 [--temperature T --top_k K --top_p P] [--repeats R] [--sample-kernel]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
-tokens/s (batch x steps / time).
+tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
+(``sample_logits`` in place of ``argmax``; the full-recompute baseline is then skipped);
+``--repeats`` times each (batch, mode) that many times; ``--sample-kernel`` times the
+``sample_logits`` launch alone on bf16 rows of the model's padded vocabulary.
 """
 from __future__ import annotations
 
@@ -25,7 +29,13 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--recompute-new", type=int, default=32, help="tokens for the full-recompute baseline")
+    ap.add_argument("--temperature", type=float, default=0.0, help="> 0: sampled decoding")
+    ap.add_argument("--top_k", type=int, default=0)
+    ap.add_argument("--top_p", type=float, default=1.0)
+    ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--sample-kernel", action="store_true", help="time the sample_logits launch alone")
     a = ap.parse_args()
+    sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
     import torch
     from distributed_pytorch_from_scratch_amd.models import get_preset, Transformer
     from distributed_pytorch_from_scratch_amd.models.generation import generate
@@ -37,20 +47,27 @@ def main():
     m = Transformer.from_args(args).cuda()
     m.reset_parameters()
     m.eval()
+    if a.sample_kernel:
+        return sample_kernel_bench(a, m.lm_head.weight.size(0), args.vocab_size)
     for B in a.batch:
         prompt = torch.randint(0, args.vocab_size, (B, a.prompt), device="cuda")
         for mode in ("graph", "eager"):
             os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
-            generate(m, prompt, max_new_tokens=a.new)           # warm-up: GEMM choices, graph capture
-                                                                #   (reused by the same-shape call)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            generate(m, prompt, max_new_tokens=a.new)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            print(json.dumps({"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
-                              "ms_per_step": round(1000 * dt / a.new, 3),
-                              "tokens_per_s": round(B * a.new / dt, 1)}), flush=True)
+            generate(m, prompt, max_new_tokens=a.new, **sampling)   # warm-up: GEMM choices, graph capture
+                                                                    #   (reused by the same-shape call)
+            for _ in range(a.repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                generate(m, prompt, max_new_tokens=a.new, **sampling)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                rec = {"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
+                       "ms_per_step": round(1000 * dt / a.new, 3), "tokens_per_s": round(B * a.new / dt, 1)}
+                if a.temperature > 0:
+                    rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+                print(json.dumps(rec), flush=True)
+        if a.temperature > 0:
+            continue
         # reference formulation: every token re-runs the whole prefix (no cache)
         seq = prompt
         torch.cuda.synchronize()
@@ -65,6 +82,38 @@ def main():
         print(json.dumps({"model": a.model, "batch": B, "mode": "full-recompute", "prompt": a.prompt,
                           "new": a.recompute_new, "ms_per_step": round(1000 * dt / a.recompute_new, 3),
                           "tokens_per_s": round(B * a.recompute_new / dt, 1)}), flush=True)
+
+
+def sample_kernel_bench(a, ld: int, vocab: int):
+    """us per ``sample_logits`` launch (device events over 200 launches) on (B, ld) bf16 rows."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.ops import _ext
+    C = _ext.require()
+    T = a.temperature if a.temperature > 0 else 1.0
+    for B in a.batch:
+        x = (torch.randn(B, ld, device="cuda") * 4).bfloat16()
+        pos = torch.zeros(B, dtype=torch.int64, device="cuda")
+        # 200 launches in one graph: the replay is not paced by the host's launch rate
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(3):
+                C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(200):
+                C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
+        g.replay()
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            print(json.dumps({"kernel": "sample_logits", "batch": B, "vocab": vocab, "ld": ld, "temperature": T,
+                              "top_k": a.top_k, "top_p": a.top_p, "us_per_call": round(5 * e0.elapsed_time(e1), 2)}),
+                  flush=True)
 
 
 if __name__ == "__main__":
