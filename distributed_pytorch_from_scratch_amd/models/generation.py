@@ -135,7 +135,7 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     logits (B, vocab) fp32); the ids are the ``argmax``, or with ``sample`` = (temperature,
     top_k, top_p, seed) a draw keyed on (seed, row, ``pos``).  Touches no host state:
     graph-capturable."""
-    from .fused_engine import _Layer
+    from .engine_common import _Layer
     if model.args.norm != "rmsnorm":
         return _decode_step_modules(model, ids, pos, cache, sample)
     B = ids.size(0)

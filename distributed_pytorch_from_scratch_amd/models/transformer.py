@@ -261,7 +261,8 @@ class Transformer(nn.Module):
         compute d logits in the forward, in the same pass over the logits as the loss."""
         if self.fused_supported():
             self._ce_unit_grad = bool(unit_grad)
-            from .fused_engine import DecoderTrainFn, collect_params
+            from .engine_common import collect_params
+            from .fused_engine import DecoderTrainFn
             assert input_ids.size(1) <= self.args.maxlen
             p = pm.pgm
             fn = DecoderTrainFn

@@ -264,7 +264,7 @@ def allreduce_sequence_parallel_grads(model: torch.nn.Module) -> None:
     a = getattr(model, "_dpfs_grad_arena", None)
     if a is not None and "sprep" in a.ranges:
         # the SP fused engine keeps every replicated gradient in one contiguous arena range
-        # ("sprep", fused_engine.arena_groups): one in-place all-reduce, no pack / copy back
+        # ("sprep", models/engine_common.arena_groups): one in-place all-reduce, no pack / copy back
         lo, hi = a.ranges["sprep"]
         rep = [q for q in model.parameters() if getattr(q, "sequence_parallel_grad", False) and q.grad is not None]
         base, end = a.buf.data_ptr(), a.buf.data_ptr() + 4 * a.numel
