@@ -1,0 +1,177 @@
+#include "common.h"
+
+namespace {
+
+// ----------------------------------------------------------------------------- decode --
+void check_cache(const torch::Tensor& c, const char* name) {
+  check_cuda(c, name);
+  TORCH_CHECK(c.dim() == 4 && c.is_contiguous() && c.scalar_type() == torch::kBFloat16, name,
+              " must be a contiguous bf16 (B, T_max, H, hd) cache");
+}
+
+void check_len(const torch::Tensor& len) {
+  check_cuda(len, "len");
+  TORCH_CHECK(len.scalar_type() == torch::kInt32 && len.numel() == 1, "len must be a device int32 scalar");
+}
+
+// o[B, H*hd] = softmax(q k^T * scale) v over keys [0, *len] of the cache (one query per
+// sequence and head).  q: [B, >= H*hd] rows (e.g. the q part of the packed qkv row).
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor len, double scale) {
+  check_rowmajor(q, "q");
+  check_cache(kc, "k_cache");
+  check_cache(vc, "v_cache");
+  check_len(len);
+  TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
+  const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, "attn_decode: head_dim 32, 64 or 128");
+  TORCH_CHECK(q.size(0) == B && q.size(1) >= H * hd && q.stride(0) % 8 == 0 && q.scalar_type() == torch::kBFloat16,
+              "attn_decode: q rows");
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({B, H * hd}, q.options());
+  const int ns = dpfs_decode_nsplit((int)Tmax);
+  auto part = torch::empty({B * H * ns * (hd + 2)}, q.options().dtype(torch::kFloat32));
+  dpfs_attn_decode(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(), o.data_ptr(), H * hd,
+                   part.data_ptr<float>(), (int)B, (int)H, (int)hd, (int)Tmax, (float)scale, stream());
+  return o;
+}
+
+// Write the k / v parts of the packed qkv rows [B, 3*H*hd] into the caches at row *len.
+void kv_append(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc, torch::Tensor len) {
+  check_rowmajor(qkv, "qkv");
+  check_cache(kc, "k_cache");
+  check_cache(vc, "v_cache");
+  check_len(len);
+  const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * H * hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16,
+              "kv_append: qkv must be [B, 3*H*hd] bf16");
+  const at::DeviceGuard g(qkv.device());
+  const char* p = static_cast<const char*>(qkv.data_ptr());
+  dpfs_kv_append(p + H * hd * 2, p + 2 * H * hd * 2, qkv.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(),
+                 (int)B, (int)H, (int)hd, (int)Tmax, stream());
+}
+
+// y[M, N] = x[M, K] w[N, K]^T (+ bias) for M <= 16 (decode-step projections); with swiglu,
+// x is the packed [M, 2K] gate|up output and the operand is silu(gate) * up.
+bool gemv_nt_ok(torch::Tensor x, torch::Tensor w, bool swiglu) {
+  if (!x.is_cuda() || x.dim() != 2 || w.dim() != 2 || x.scalar_type() != torch::kBFloat16 ||
+      w.scalar_type() != torch::kBFloat16 || x.stride(1) != 1 || w.stride(1) != 1)
+    return false;
+  const int64_t K = w.size(1);
+  if (x.size(1) != (swiglu ? 2 * K : K)) return false;
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 || reinterpret_cast<uintptr_t>(w.data_ptr()) % 16)
+    return false;   // 16-byte operand loads
+  return dpfs_gemv16_ok((int)x.size(0), (int)w.size(0), (int)K, x.stride(0), w.stride(0)) != 0;
+}
+
+torch::Tensor gemv_nt(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, bool swiglu) {
+  TORCH_CHECK(gemv_nt_ok(x, w, swiglu), "gemv_nt: needs bf16 row-major x [M <= 16, K or 2K], w [N, K], K % 32 == 0");
+  const int64_t M = x.size(0), N = w.size(0), K = w.size(1);
+  const at::DeviceGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  dpfs_gemv16(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M,
+              (int)N, (int)K, swiglu ? 1 : 0, stream());
+  return y;
+}
+
+// rope_ on the q and k heads of the packed qkv rows + kv_append of the rotated k and v rows
+// at *len, one kernel (decode step).
+void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kc, torch::Tensor vc,
+                 torch::Tensor len) {
+  check_rowmajor(qkv, "qkv");
+  check_cache(kc, "k_cache");
+  check_cache(vc, "v_cache");
+  check_len(len);
+  const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * H * hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16 && hd % 16 == 0,
+              "rope_append: qkv must be [B, 3*H*hd] bf16, hd % 16 == 0");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == B,
+              "rope_append: pos must be contiguous int64 [B]");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kFloat32 && table.is_contiguous() &&
+                  table.size(1) == hd,
+              "rope_append: table must be fp32 [maxlen, hd]");
+  const at::DeviceGuard g(qkv.device());
+  dpfs_rope_append(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(), table.data_ptr<float>(), kc.data_ptr(),
+                   vc.data_ptr(), len.data_ptr<int>(), (int)B, (int)H, (int)hd, (int)Tmax, stream());
+}
+
+// Per-tensor fp8 quantisation with current scaling: (q, inv) with q = sat(x * FMAX / amax)
+// in float8_e4m3fn (fmt 0) or float8_e5m2 (fmt 1), inv = amax / FMAX as an fp32 0-d tensor
+// (the scale torch._scaled_mm multiplies back).  No host synchronisation.
+std::vector<torch::Tensor> fp8_quant(torch::Tensor x, int64_t fmt) {
+  check_cuda(x, "x");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous() && x.numel() % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "fp8_quant: x must be contiguous bf16 with numel % 8 == 0");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "fp8_quant: fmt 0 (e4m3) or 1 (e5m2)");
+  const at::DeviceGuard g(x.device());
+  auto q = torch::empty(x.sizes(), x.options().dtype(fmt == 0 ? at::kFloat8_e4m3fn : at::kFloat8_e5m2));
+  auto inv = torch::empty({}, x.options().dtype(torch::kFloat32));
+  auto work = torch::empty({dpfs_fp8_work_floats()}, x.options().dtype(torch::kFloat32));
+  if (x.numel())
+    dpfs_fp8_quant(x.data_ptr(), x.numel(), (int)fmt, q.data_ptr(), inv.data_ptr<float>(), work.data_ptr<float>(),
+                   stream());
+  else
+    inv.fill_(1.0);
+  return {q, inv};
+}
+
+// *len += 1 and pos[:] = *len on the device (end of a decode step; graph-replayable).
+void step_advance(torch::Tensor len, torch::Tensor pos) {
+  check_len(len);
+  check_cuda(pos, "pos");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt64 && pos.is_contiguous(), "pos must be contiguous int64");
+  const at::DeviceGuard g(len.device());
+  dpfs_step_advance(len.data_ptr<int>(), pos.data_ptr<int64_t>(), (int)pos.numel(), stream());
+}
+
+// Temperature / top-k / top-p sampling of one token per row (kernels/sample.hip): logits
+// [B, >= vocab] bf16 / fp32 with unit column stride, columns >= vocab are padding.  top_k 0 or
+// >= vocab and top_p 1 are off.  The uniform of row b is Philox4x32-10(key seed, counter
+// (pos[b], b, 0)) unless `u` [B] supplies it (tests).  Returns (ids int64, kept int32, thresh
+// fp32, u fp32), each [B].  No host synchronisation: graph-capturable.
+py::tuple sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
+                        int64_t seed, torch::Tensor pos, c10::optional<torch::Tensor> u) {
+  check_rowmajor(logits, "logits");
+  const int dt = dcode(logits);
+  const int64_t B = logits.size(0), ld = logits.stride(0), vec = dt == 1 ? 8 : 4;
+  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab < (1LL << 31) && (B <= 1 || ld >= logits.size(1)),
+              "sample_logits: 1 <= vocab <= ld, got vocab ", vocab, " for rows of ", logits.size(1));
+  TORCH_CHECK(temperature > 0.0, "sample_logits: temperature must be > 0, got ", temperature);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0, got ", top_k);
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == B,
+              "sample_logits: pos must be contiguous int64 [B]");
+  const float* up = opt_f32(u, B, "u");
+  const at::DeviceGuard g(logits.device());
+  auto ids = torch::empty({B}, pos.options());
+  auto kept = torch::empty({B}, pos.options().dtype(torch::kInt32));
+  auto thresh = torch::empty({B}, pos.options().dtype(torch::kFloat32));
+  auto uo = torch::empty({B}, pos.options().dtype(torch::kFloat32));
+  // 16-byte row loads need aligned rows whose last vector lies inside the row
+  const int64_t esz = dt == 1 ? 2 : 4;
+  const bool vec_ok = reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 && (B <= 1 || ld * esz % 16 == 0) &&
+                      (vocab + vec - 1) / vec * vec <= logits.size(1);
+  const int k = (int)std::min<int64_t>(top_k, vocab);
+  dpfs_sample_logits(logits.data_ptr(), dt, ld, (int)B, (int)vocab, vec_ok ? 1 : 0, (float)(1.0 / temperature), k, top_p,
+                     (unsigned long long)seed, pos.data_ptr<int64_t>(), up, ids.data_ptr<int64_t>(),
+                     kept.data_ptr<int>(), thresh.data_ptr<float>(), uo.data_ptr<float>(), stream());
+  return py::make_tuple(ids, kept, thresh, uo);
+}
+
+}  // namespace
+
+void bind_decode(py::module_& m) {
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"),
+        py::arg("scale"));
+  m.def("kv_append", &kv_append, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"));
+  m.def("step_advance", &step_advance, py::arg("len"), py::arg("pos"));
+  m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
+  m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
+  m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("len"));
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seed"), py::arg("pos"), py::arg("u") = py::none());
+}

@@ -13,6 +13,7 @@
 //   1 NN  y[M,N]  = a[M,K] b[K,N]                      ->  D^T[N,M] = b^T a^T
 //   2 TN  y[M,N] (+)= a[K,M]^T b[K,N], y fp32          ->  D^T[N,M] = b^T op_T(a^T)
 #include <hip/hip_runtime.h>
+#include "../dpfs_api.h"
 #include <hipblaslt/hipblaslt.h>
 
 #include <cstdio>

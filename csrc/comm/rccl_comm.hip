@@ -9,6 +9,7 @@
 // Linked against the librccl.so that PyTorch itself loads (torch/lib, build_ext.py), so the
 // process holds one RCCL instance whichever path opens a communicator.
 #include <hip/hip_runtime.h>
+#include "../dpfs_api.h"
 #include <rccl/rccl.h>
 
 #include <cstdio>

@@ -41,6 +41,7 @@
 // Every wait is bounded (s_memrealtime, 100 MHz): on timeout the kernel records an error in a
 // host-mapped word and exits, so a broken peer can never hang the GPU.
 #include <hip/hip_runtime.h>
+#include "../dpfs_api.h"
 #include <stdint.h>
 #include <string.h>
 
@@ -312,8 +313,6 @@ bool ok(hipError_t e, const char* what) {
 }
 
 }  // namespace
-
-extern "C" void dpfs_xgmi_destroy(void* h);
 
 extern "C" const char* dpfs_xgmi_last_error() { return g_msg; }
 

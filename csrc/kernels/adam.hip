@@ -10,6 +10,7 @@
 // correction with the step count).  Optional device-side grad scale (clip coefficient)
 // keeps gradient clipping free of host syncs.
 #include "common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 

@@ -23,6 +23,7 @@
 //    reads (ds_read_b128) and for transposed reads (ds_read_b64_tr_b16).
 //  * causal: key tiles above the diagonal are never visited; heaviest q-blocks launch first.
 #include "common.h"
+#include "../dpfs_api.h"
 #include "attn_common.h"
 
 #include <algorithm>
@@ -1969,13 +1970,6 @@ extern "C" void dpfs_attn_fwd(const void* q, const void* k, const void* v, void*
   HD_DISPATCH(hd, attn_fwd_k<HD_><<<grid, 256, 0, s>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,
                                                             lse, T, H, ldq, ldk, ldv, ldo, scale, causal));
 }
-
-// attention_fused.hip (its own translation unit: asm-owned AGPR accumulators)
-extern "C" void dpfs_attn_bwd_dkdv4(int items, const void* q, const void* k, const void* v, const void* dout,
-                                    const float* lsn, const float* ndel, void* dk, void* dv, int T, int H, int BH,
-                                    long long ldq, long long ldk, long long ldv, long long lddo, long long lddk,
-                                    long long lddv, float scale, int causal, const int64_t* rope_pos,
-                                    const float* rope_tab, float* pk, float* pv, int prefetch, hipStream_t s);
 
 // delta: workspace [2][B, H, T] fp32: -delta (rowsum(dO*O)) and -lse/scale, written by the dQ kernel.
 // Backward kernel pair (`impl`): 0 = auto (4 at head_dim 64 / 128, 2 otherwise), 2 =

@@ -3,6 +3,7 @@
 // so the compiler keeps its MFMA accumulators in VGPRs; the long-lived dK^T / dV^T
 // accumulators live in asm-owned AGPRs.
 #include "attn_common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 

@@ -20,6 +20,7 @@
 // new token's (RoPE-rotated) key / value rows at row *len_ptr; step_advance_k bumps the
 // length and the position ids on the device at the end of the step.
 #include "common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 

@@ -4,6 +4,7 @@
 // All use 16-byte vector accesses per lane (8 bf16) and grid-stride loops with grids capped
 // at 2048 blocks (Guideline 11: ~256 CUs x 8 blocks).
 #include "common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 

@@ -13,6 +13,7 @@
 // Cross-entropy: per-row online max / sum-exp over the local shard in ONE pass (fp32), the
 // target logit if owned; backward writes (softmax - onehot) * g in place over the logits.
 #include "common.h"
+#include "../dpfs_api.h"
 
 #include <algorithm>
 
@@ -703,9 +704,6 @@ __global__ __launch_bounds__(256) void emb_seg_k(const int* __restrict__ keys, i
 }  // namespace dpfs
 
 using namespace dpfs;
-
-extern "C" int dpfs_colsum_plan(int M, int cblocks, int target_blocks, int* rpc);
-extern "C" void dpfs_colsum_rows_small(const float* part, float* out, int rows, int N, hipStream_t s);
 
 // Vector width of the CE backward: 16 B when every row is 16-B aligned, else element-wise.
 static inline int ce_vec(int dtype, int V) {

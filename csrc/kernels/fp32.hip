@@ -17,6 +17,7 @@
 //    computes S = Q K^T with the key on the lane.  K / V / Q / dO tiles are fp32 in LDS with
 //    a row stride of HD + 1 floats (conflict-free column reads).  Only the log-sum-exp is saved.
 #include "common.h"
+#include "../dpfs_api.h"
 
 #include <algorithm>
 

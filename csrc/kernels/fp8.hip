@@ -7,6 +7,7 @@
 // whole quantisation is stream-ordered and graph-capturable.  The fp32 scale arithmetic matches the
 // PyTorch oracle (ops/fp8.py) operation for operation, so the fp8 bytes are identical.
 #include "common.h"
+#include "../dpfs_api.h"
 #include <hip/hip_fp8.h>
 
 namespace dpfs {

@@ -29,6 +29,7 @@
 //  * split-K over blockIdx.y for the skinny-output wgrad: fp32 slabs + fixed-order reduction
 //    (deterministic, no float atomics).
 #include "common.h"
+#include "../dpfs_api.h"
 
 #include <algorithm>
 
@@ -899,22 +900,11 @@ extern "C" void dpfs_gemm_set_workspace(float* ws, long long n) {
   g_ws = ws;
   g_ws_floats = n;
 }
-extern "C" void dpfs_rope(int dtype, void* qkv, const int64_t* pos, const float* table, int M, int ld, int n_heads,
-                          int hd, int inverse, hipStream_t s);
 static void dpfs_rope_after_gemm(void* C, RopeArgs r, int M, int ldc, hipStream_t s) {
   dpfs_rope(1, C, r.pos, r.tab, M, ldc, r.cols / r.hd, r.hd, 0, s);
 }
 
-// v4 (csrc/kernels/gemm4.hip: one wave per SIMD, 128 x 128 per wave).  Bit mask of the
-// layouts it carries: 1 = NT, 2 = NN, 4 = TN (fp32 split-K).  Where the launcher declines a
-// shape (32-bit spans, alignment) the v3 kernel runs.
-extern "C" bool dpfs_gemm4_launch(int layout, int out_f32, const void* A, const void* B, void* C, const float* bias,
-                                  int M, int N, int K, int lda, int ldb, int ldc, int kps, int splits,
-                                  long long slab_stride, unsigned a_bytes, unsigned b_bytes, const int64_t* rope_pos,
-                                  const float* rope_tab, int rope_cols, int rope_hd, const void* A2, const void* B2,
-                                  int k_switch, int lda2, int ldb2, unsigned a2_bytes, unsigned b2_bytes,
-                                  int bn_force, hipStream_t s);
-
+// v4 is dpfs_gemm4_launch (csrc/kernels/gemm4.hip: one wave per SIMD, 128 x 128 per wave).
 // Per-call kernel variant (an argument of every GEMM entry point, never process state):
 //   0 = v4 with its per-shape tile width (the default for every layout),
 //   1 / 2 = v4 with the 256 / 192 tile width forced (non-split bf16 NT / NN),
@@ -927,8 +917,6 @@ static int v4_bn(int variant) {
   const int w = variant & 3;
   return (w == 1 ? 256 : (w == 2 ? 192 : 0)) | ((variant & 4) ? 0x100 : 0) | ((variant & 8) ? 0x200 : 0);
 }
-extern "C" void dpfs_gemm4_set_sk_ws(float* p, long long n);
-extern "C" long long dpfs_gemm4_sk_ws(int M, int N, int K);
 
 extern "C" long long dpfs_gemm_bf16_ws(int M, int N, int K) {
   const int S = bf16_splits(M, N, K);

@@ -34,6 +34,7 @@
 //    ds_read_b64_tr_b16 hardware transpose, through inline asm: see ds_tr16).  The swizzle
 //    is applied on the DMA SOURCE address (LDS-DMA writes lane-linear 1 KiB pieces).
 #include "common.h"
+#include "../dpfs_api.h"
 
 #include <algorithm>
 #include <type_traits>

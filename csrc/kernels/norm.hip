@@ -12,6 +12,7 @@
 // across blocks by a second column-sum kernel.  No float atomics anywhere: the replicated
 // norm weights must get bitwise-identical grads on every TP rank.
 #include "common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 
@@ -306,14 +307,6 @@ int norm_bwd_grid(int M) {
 }  // namespace dpfs
 
 using namespace dpfs;
-
-extern "C" void dpfs_colsum_f32(const float* x, float* out, float* ws, int M, int N, hipStream_t s);
-extern "C" void dpfs_colsum_rows_small(const float* part, float* out, int rows, int N, hipStream_t s);
-extern "C" void dpfs_colsum_rows_split(const float* part, float* out, float* out2, int split, int rows, int N,
-                                       hipStream_t s);
-extern "C" void dpfs_colsum_f32_split(const float* x, float* out, float* out2, int split, float* ws, int M, int N,
-                                      hipStream_t s);
-extern "C" long long dpfs_colsum_ws(int M, int N);
 
 extern "C" int dpfs_norm_bwd_grid(int M) { return norm_bwd_grid(M); }
 // Total fp32 workspace of dpfs_norm_bwd: the block partials (x2 for LayerNorm / mode 2).

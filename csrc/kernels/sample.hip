@@ -26,6 +26,7 @@
 // rescans it.  The row is re-read from L2 by every pass (a 50,304-column bf16 row is
 // 100 KB); it is never staged in LDS.
 #include "common.h"
+#include "../dpfs_api.h"
 
 namespace dpfs {
 namespace {

@@ -4,7 +4,8 @@ Two-stage native build, no hipify, no JIT cache:
 
 1. every ``csrc/{kernels,comm,blas}/*.hip`` -> ``hipcc --offload-arch=gfx950 -O3 -c`` (pure HIP,
    no torch headers, so each file compiles in seconds; parallel; mtime-cached);
-2. ``csrc/bindings.cpp`` -> ``g++`` against the PyTorch headers (host code only);
+2. every ``csrc/bindings/*.cpp`` -> ``g++`` against the PyTorch headers (host code only), in the
+   same pool; both sides include ``csrc/dpfs_api.h``, the one declaration of the C ABI between them;
 3. link with the ROCm runtime, RCCL and hipBLASLt that PyTorch itself ships (``torch/lib``), so
    the process has exactly one instance of each.
 
@@ -69,7 +70,8 @@ def build(jobs: int = 8, force: bool = False, verbose: bool = True, kernel_asser
     obj_dir = OBJ + ("_kassert" if kernel_assert else "")
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
-    headers = glob.glob(os.path.join(CSRC, "kernels", "*.h")) + glob.glob(os.path.join(CSRC, "comm", "*.h"))
+    api = os.path.join(CSRC, "dpfs_api.h")
+    headers = [api] + glob.glob(os.path.join(CSRC, "kernels", "*.h")) + glob.glob(os.path.join(CSRC, "comm", "*.h"))
     kernels = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip"))) + \
         sorted(glob.glob(os.path.join(CSRC, "comm", "*.hip"))) + \
         sorted(glob.glob(os.path.join(CSRC, "blas", "*.hip")))
@@ -84,25 +86,28 @@ def build(jobs: int = 8, force: bool = False, verbose: bool = True, kernel_asser
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     py_inc = sysconfig.get_paths()["include"]
     inc = ce.include_paths(device_type="cuda") if "device_type" in ce.include_paths.__code__.co_varnames else ce.include_paths(cuda=True)
-    b_src = os.path.join(CSRC, "bindings.cpp")
-    b_obj = os.path.join(obj_dir, "bindings.o")
+    bindings = sorted(glob.glob(os.path.join(CSRC, "bindings", "*.cpp")))
+    b_deps = [api, os.path.join(CSRC, "bindings", "common.h")]
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
     cxx_flags = ["-O2", "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                  f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_EXTENSION_NAME=" + ("_C_kassert" if kernel_assert else "_C"), "-DTORCH_API_INCLUDE_EXTENSION_H",
                  "-I" + py_inc, "-I" + os.path.join(rocm, "include"), "-Wno-deprecated-declarations"]
     for i in inc:
         cxx_flags.append("-I" + i)
-    if force or _newer([b_src], b_obj):
-        jobs_list.append(["g++"] + cxx_flags + ["-c", b_src, "-o", b_obj])
+    for b in bindings:
+        o = os.path.join(obj_dir, os.path.basename(b) + ".o")
+        if force or _newer([b] + b_deps, o):
+            jobs_list.append(["g++"] + cxx_flags + ["-c", b, "-o", o])
 
     if jobs_list:
+        jobs_list.sort(key=lambda c: -os.path.getsize(c[-3]))   # the largest sources first: gemm4.hip alone is most of the wall time
         with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
             futs = [ex.submit(_run, c) for c in jobs_list]
             for f, c in zip(futs, jobs_list):
                 f.result()
                 if verbose:
                     print("[build_ext] compiled", os.path.basename(c[-1]), flush=True)
-    objs = [os.path.join(obj_dir, os.path.basename(k) + ".o") for k in kernels] + [b_obj]
+    objs = [os.path.join(obj_dir, os.path.basename(f) + ".o") for f in kernels + bindings]
     out = ext_path(kernel_assert)
     if force or jobs_list or not os.path.exists(out):
         tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
