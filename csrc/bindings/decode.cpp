@@ -9,9 +9,14 @@ void check_cache(const torch::Tensor& c, const char* name) {
               " must be a contiguous bf16 (B, T_max, H, hd) cache");
 }
 
-void check_len(const torch::Tensor& len) {
+// The cache length: one int32 for the whole batch (false: the uniform kernels), or one per
+// sequence, B of them (true: the per-row kernels; at B == 1 the two coincide).
+bool check_len(const torch::Tensor& len, int64_t B) {
   check_cuda(len, "len");
-  TORCH_CHECK(len.scalar_type() == torch::kInt32 && len.numel() == 1, "len must be a device int32 scalar");
+  TORCH_CHECK(len.scalar_type() == torch::kInt32 && len.is_contiguous() && (len.numel() == 1 || len.numel() == B),
+              "len must be a contiguous device int32 tensor of 1 or B = ", B, " elements, got ", len.numel(), " of ",
+              len.scalar_type());
+  return len.numel() != 1;
 }
 
 // o[B, H*hd] = softmax(q k^T * scale) v over keys [0, *len] of the cache (one query per
@@ -20,9 +25,9 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
   check_rowmajor(q, "q");
   check_cache(kc, "k_cache");
   check_cache(vc, "v_cache");
-  check_len(len);
   TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
   const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  const bool rows = check_len(len, B);
   TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, "attn_decode: head_dim 32, 64 or 128");
   TORCH_CHECK(q.size(0) == B && q.size(1) >= H * hd && q.stride(0) % 8 == 0 && q.scalar_type() == torch::kBFloat16,
               "attn_decode: q rows");
@@ -30,8 +35,9 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
   auto o = torch::empty({B, H * hd}, q.options());
   const int ns = dpfs_decode_nsplit((int)Tmax);
   auto part = torch::empty({B * H * ns * (hd + 2)}, q.options().dtype(torch::kFloat32));
-  dpfs_attn_decode(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(), o.data_ptr(), H * hd,
-                   part.data_ptr<float>(), (int)B, (int)H, (int)hd, (int)Tmax, (float)scale, stream());
+  (rows ? dpfs_attn_decode_rows : dpfs_attn_decode)(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(),
+                                                    len.data_ptr<int>(), o.data_ptr(), H * hd, part.data_ptr<float>(),
+                                                    (int)B, (int)H, (int)hd, (int)Tmax, (float)scale, stream());
   return o;
 }
 
@@ -40,15 +46,17 @@ void kv_append(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc, torch::Ten
   check_rowmajor(qkv, "qkv");
   check_cache(kc, "k_cache");
   check_cache(vc, "v_cache");
-  check_len(len);
+  TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
   const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  const bool rows = check_len(len, B);
   TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * H * hd && qkv.stride(0) % 8 == 0 &&
                   qkv.scalar_type() == torch::kBFloat16,
               "kv_append: qkv must be [B, 3*H*hd] bf16");
   const at::DeviceGuard g(qkv.device());
   const char* p = static_cast<const char*>(qkv.data_ptr());
-  dpfs_kv_append(p + H * hd * 2, p + 2 * H * hd * 2, qkv.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(),
-                 (int)B, (int)H, (int)hd, (int)Tmax, stream());
+  (rows ? dpfs_kv_append_rows : dpfs_kv_append)(p + H * hd * 2, p + 2 * H * hd * 2, qkv.stride(0), kc.data_ptr(),
+                                                vc.data_ptr(), len.data_ptr<int>(), (int)B, (int)H, (int)hd, (int)Tmax,
+                                                stream());
 }
 
 // y[M, N] = x[M, K] w[N, K]^T (+ bias) for M <= 16 (decode-step projections); with swiglu,
@@ -81,8 +89,9 @@ void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torc
   check_rowmajor(qkv, "qkv");
   check_cache(kc, "k_cache");
   check_cache(vc, "v_cache");
-  check_len(len);
+  TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
   const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  const bool rows = check_len(len, B);
   TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * H * hd && qkv.stride(0) % 8 == 0 &&
                   qkv.scalar_type() == torch::kBFloat16 && hd % 16 == 0,
               "rope_append: qkv must be [B, 3*H*hd] bf16, hd % 16 == 0");
@@ -92,8 +101,9 @@ void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torc
                   table.size(1) == hd,
               "rope_append: table must be fp32 [maxlen, hd]");
   const at::DeviceGuard g(qkv.device());
-  dpfs_rope_append(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(), table.data_ptr<float>(), kc.data_ptr(),
-                   vc.data_ptr(), len.data_ptr<int>(), (int)B, (int)H, (int)hd, (int)Tmax, stream());
+  (rows ? dpfs_rope_append_rows : dpfs_rope_append)(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(),
+                                                    table.data_ptr<float>(), kc.data_ptr(), vc.data_ptr(),
+                                                    len.data_ptr<int>(), (int)B, (int)H, (int)hd, (int)Tmax, stream());
 }
 
 // Per-tensor fp8 quantisation with current scaling: (q, inv) with q = sat(x * FMAX / amax)
@@ -117,13 +127,33 @@ std::vector<torch::Tensor> fp8_quant(torch::Tensor x, int64_t fmt) {
   return {q, inv};
 }
 
-// *len += 1 and pos[:] = *len on the device (end of a decode step; graph-replayable).
+// *len += 1 and pos[:] = *len on the device (end of a decode step; graph-replayable).  The
+// uniform form only: a per-row len goes through step_advance_rows, which needs the capacity.
 void step_advance(torch::Tensor len, torch::Tensor pos) {
-  check_len(len);
+  check_cuda(len, "len");
+  TORCH_CHECK(len.scalar_type() == torch::kInt32 && len.numel() == 1,
+              "step_advance: len must be a device int32 scalar (per-row lengths: _step_advance_rows(len, pos, t_max))");
   check_cuda(pos, "pos");
   TORCH_CHECK(pos.scalar_type() == torch::kInt64 && pos.is_contiguous(), "pos must be contiguous int64");
   const at::DeviceGuard g(len.device());
   dpfs_step_advance(len.data_ptr<int>(), pos.data_ptr<int64_t>(), (int)pos.numel(), stream());
+}
+
+// Per-row end of a decode step: len[b] = min(len[b] + 1, t_max) and pos[b] = min(len[b],
+// t_max - 1) for each of the B sequences, so a row that fills its cache (capacity t_max) is
+// frozen there.  Bound as _step_advance_rows: the module's recorded public surface
+// (tests/golden/ext_api.txt) is left as it is.
+void step_advance_rows(torch::Tensor len, torch::Tensor pos, int64_t t_max) {
+  check_cuda(pos, "pos");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt64 && pos.is_contiguous(), "pos must be contiguous int64");
+  const int64_t B = pos.numel();
+  check_len(len, B);
+  TORCH_CHECK(len.numel() == B, "step_advance_rows: len must have one element per pos entry, got ", len.numel(),
+              " for ", B);
+  TORCH_CHECK(len.device() == pos.device(), "len and pos must be on the same device");
+  TORCH_CHECK(t_max >= 1 && t_max < (1LL << 31), "step_advance_rows: t_max must be in [1, 2^31), got ", t_max);
+  const at::DeviceGuard g(len.device());
+  dpfs_step_advance_rows(len.data_ptr<int>(), pos.data_ptr<int64_t>(), (int)B, (int)t_max, stream());
 }
 
 // Temperature / top-k / top-p sampling of one token per row (kernels/sample.hip): logits
@@ -167,6 +197,7 @@ void bind_decode(py::module_& m) {
         py::arg("scale"));
   m.def("kv_append", &kv_append, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"));
   m.def("step_advance", &step_advance, py::arg("len"), py::arg("pos"));
+  m.def("_step_advance_rows", &step_advance_rows, py::arg("len"), py::arg("pos"), py::arg("t_max"));
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);

@@ -63,6 +63,14 @@ void dpfs_gemv16(const void* A, long long lda, const void* W, long long ldw, con
                  long long ldy, int M, int N, int K, int swiglu, hipStream_t s);
 void dpfs_rope_append(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kc, void* vc,
                       const int* len_ptr, int B, int H, int HD, int Tmax, hipStream_t s);
+// per-row lengths (ragged batches): len[B], sequence b uses len[b]; step_advance_rows clamps at t_max
+void dpfs_attn_decode_rows(const void* q, long long ldq, const void* kc, const void* vc, const int* len, void* o,
+                           long long ldo, float* part, int B, int H, int HD, int Tmax, float scale, hipStream_t s);
+void dpfs_kv_append_rows(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc, const int* len, int B,
+                         int H, int HD, int Tmax, hipStream_t s);
+void dpfs_rope_append_rows(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kc, void* vc,
+                           const int* len, int B, int H, int HD, int Tmax, hipStream_t s);
+void dpfs_step_advance_rows(int* len, int64_t* pos, int B, int t_max, hipStream_t s);
 
 // kernels/elementwise.hip
 void dpfs_swiglu_fwd(int dtype, const void* gu, void* h, int M, int F, int perm, hipStream_t s);

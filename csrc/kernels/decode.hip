@@ -19,6 +19,13 @@
 // replayed for every token (splits past the length exit at once).  kv_append_k writes the
 // new token's (RoPE-rotated) key / value rows at row *len_ptr; step_advance_k bumps the
 // length and the position ids on the device at the end of the step.
+//
+// Ragged batches: every length-reading kernel is a template on ROWS.  ROWS = false is the
+// uniform form above (one int32 for the whole batch); ROWS = true reads len[b], one int32 per
+// sequence, and is otherwise the same code, so a row of length L computes exactly what the
+// uniform kernel computes at *len = L.  step_advance_rows_k clamps every row at the cache
+// capacity: a row that reaches it is frozen (appends nothing, attends inside its cache rows,
+// keeps its position inside the RoPE table) while the shorter rows of the batch go on.
 #include "common.h"
 #include "../dpfs_api.h"
 
@@ -26,14 +33,15 @@ namespace dpfs {
 
 constexpr int kSplit = 256;   // keys per workgroup
 
-template <int HD>
+template <int HD, bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restrict__ q, long long ldq,
                                                           const bf16* __restrict__ kc, const bf16* __restrict__ vc,
                                                           const int* __restrict__ len_ptr, int H, int Tmax,
                                                           float scale, float* __restrict__ part) {
   constexpr int NV = HD / 8;               // 16-byte vectors per row
   const int split = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int L = min(*len_ptr + 1, Tmax);  // cached keys + the token being decoded
+  KASSERT(!ROWS || len_ptr[b] >= 0, "cache length %d of sequence %d", len_ptr[b], b);
+  const int L = min(len_ptr[ROWS ? b : 0] + 1, Tmax);  // cached keys + the token being decoded
   const int k0 = split * kSplit;
   float* out = part + ((long long)bh * gridDim.x + split) * (HD + 2);
   if (k0 >= L) return;                     // the combine kernel never reads this split
@@ -134,12 +142,12 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
   }
 }
 
-template <int HD>
+template <int HD, bool ROWS>
 __global__ __launch_bounds__(64) void attn_decode_combine_k(const float* __restrict__ part, int nsplit,
                                                            const int* __restrict__ len_ptr, bf16* __restrict__ o,
                                                            long long ldo, int H) {
   const int bh = blockIdx.x, b = bh / H, h = bh % H;
-  const int L = min(*len_ptr + 1, nsplit * kSplit);
+  const int L = min(len_ptr[ROWS ? b : 0] + 1, nsplit * kSplit);
   const int live = (L + kSplit - 1) / kSplit;
   const float* p = part + (long long)bh * nsplit * (HD + 2);
   float M = -INFINITY;
@@ -165,17 +173,24 @@ __global__ __launch_bounds__(64) void attn_decode_combine_k(const float* __restr
     if (on) orow[threadIdx.x + 64 * j] = (bf16)(acc[j] * inv);
 }
 
-// cache[b, *len, h, :] = src rows (k and v parts of the packed qkv row of sequence b)
+// cache[b, len, h, :] = src rows (k and v parts of the packed qkv row of sequence b), len =
+// *len_ptr, or with ROWS len_ptr[b]
+template <bool ROWS>
 __global__ __launch_bounds__(256) void kv_append_k(const bf16* __restrict__ ksrc, const bf16* __restrict__ vsrc,
                                                   long long ld, bf16* __restrict__ kc, bf16* __restrict__ vc,
                                                   const int* __restrict__ len_ptr, int B, int H, int HD, int Tmax) {
-  const int t = *len_ptr;
-  if (t < 0 || t >= Tmax) return;          // full cache: nothing to append (never out of bounds)
+  const int t0 = ROWS ? 0 : *len_ptr;
+  if (!ROWS && (t0 < 0 || t0 >= Tmax)) return;   // full cache: nothing to append (never out of bounds)
   const int nv = H * HD / 8;               // 16-byte vectors per token row
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2 * B * nv; i += gridDim.x * blockDim.x) {
     const int isv = i >= B * nv;
     const int j = isv ? i - B * nv : i;
     const int b = j / nv, c = j % nv;
+    const int t = ROWS ? len_ptr[b] : t0;
+    if (ROWS) {
+      KASSERT(t >= 0, "cache length %d of sequence %d", t, b);
+      if (t < 0 || t >= Tmax) continue;    // this row is full
+    }
     const bf16* src = (isv ? vsrc : ksrc) + (long long)b * ld + 8 * c;
     bf16* dst = (isv ? vc : kc) + ((long long)b * Tmax + t) * H * HD + 8 * c;
     *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
@@ -252,15 +267,17 @@ __global__ __launch_bounds__(64 * KS) void gemv16_k(const bf16* __restrict__ A, 
 }
 
 // RoPE of the q and k heads of the packed qkv rows (in place) fused with the cache append of
-// the rotated k row and the v row at row *len: one launch instead of rope_k + kv_append_k.
-// Same arithmetic and rounding as rope_vec_k (sign +1).  8 frequency pairs per thread.
+// the rotated k row and the v row at row *len (ROWS: len[b]): one launch instead of rope_k +
+// kv_append_k.  Same arithmetic and rounding as rope_vec_k (sign +1).  8 frequency pairs per
+// thread.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, long long ld,
                                                      const int64_t* __restrict__ pos,
                                                      const float* __restrict__ tab, bf16* __restrict__ kc,
                                                      bf16* __restrict__ vc, const int* __restrict__ len_ptr,
                                                      int B, int H, int HD, int Tmax) {
-  const int t = *len_ptr;
-  const bool app = t >= 0 && t < Tmax;     // full cache: rotate, append nothing
+  const int t0 = ROWS ? 0 : *len_ptr;
+  const bool app0 = ROWS || (t0 >= 0 && t0 < Tmax);   // full cache: rotate, append nothing
   const int h2 = HD / 2, q8 = h2 / 8;
   const int rot_per_b = 2 * H * q8;
   const int nrot = B * rot_per_b;
@@ -270,6 +287,9 @@ __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, lon
     if (i < nrot) {
       const int b = i / rot_per_b, r = i - b * rot_per_b;
       const int head = r / q8, f0 = (r - head * q8) * 8;
+      const int t = ROWS ? len_ptr[b] : t0;
+      KASSERT(!ROWS || t >= 0, "cache length %d of sequence %d", t, b);
+      const bool app = ROWS ? (t >= 0 && t < Tmax) : app0;
       bf16* base = qkv + (long long)b * ld + head * HD;
       KASSERT(pos[b] >= 0, "decode position %lld of sequence %d", (long long)pos[b], b);
       const float* tr = tab + pos[b] * (long long)HD;
@@ -290,8 +310,10 @@ __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, lon
         *reinterpret_cast<bf16x8*>(dst + f0) = oa;
         *reinterpret_cast<bf16x8*>(dst + h2 + f0) = ob;
       }
-    } else if (app) {
+    } else if (app0) {
       const int j = i - nrot, b = j / vpr, c = j - b * vpr;
+      const int t = ROWS ? len_ptr[b] : t0;
+      if (ROWS && (t < 0 || t >= Tmax)) continue;   // this row is full
       const bf16* src = qkv + (long long)b * ld + 2 * H * HD + 8 * c;
       bf16* dst = vc + ((long long)b * Tmax + t) * H * HD + 8 * c;
       *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
@@ -308,41 +330,74 @@ __global__ void step_advance_k(int* __restrict__ len_ptr, int64_t* __restrict__ 
   }
 }
 
+// Per-row form: len[b] = min(len[b] + 1, t_max); pos[b] = min(len[b], t_max - 1).  A row that
+// reaches t_max stays there (frozen) with its position on the last row of the RoPE table part
+// the cache covers.  One thread per sequence.
+__global__ __launch_bounds__(256) void step_advance_rows_k(int* __restrict__ len, int64_t* __restrict__ pos, int B,
+                                                           int t_max) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  KASSERT(len[b] >= 0, "cache length %d of sequence %d", len[b], b);
+  const int t = min(len[b] + 1, t_max);
+  len[b] = t;
+  pos[b] = min(t, t_max - 1);
+}
+
 }  // namespace dpfs
 
 using namespace dpfs;
 
 extern "C" int dpfs_decode_nsplit(int Tmax) { return (Tmax + kSplit - 1) / kSplit; }
 
+template <int HD, bool ROWS>
+static void launch_attn_decode(const void* q, long long ldq, const void* kc, const void* vc, const int* len_ptr, void* o,
+                               long long ldo, float* part, int B, int H, int Tmax, float scale, hipStream_t s) {
+  const int ns = dpfs_decode_nsplit(Tmax);
+  attn_decode_split_k<HD, ROWS><<<dim3(ns, B * H), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc,
+                                                                  len_ptr, H, Tmax, scale, part);
+  attn_decode_combine_k<HD, ROWS><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
+}
+
+template <bool ROWS>
+static void attn_decode_hd(const void* q, long long ldq, const void* kc, const void* vc, const int* len_ptr, void* o,
+                           long long ldo, float* part, int B, int H, int HD, int Tmax, float scale, hipStream_t s) {
+  if (HD == 32) launch_attn_decode<32, ROWS>(q, ldq, kc, vc, len_ptr, o, ldo, part, B, H, Tmax, scale, s);
+  else if (HD == 64) launch_attn_decode<64, ROWS>(q, ldq, kc, vc, len_ptr, o, ldo, part, B, H, Tmax, scale, s);
+  else launch_attn_decode<128, ROWS>(q, ldq, kc, vc, len_ptr, o, ldo, part, B, H, Tmax, scale, s);
+}
+
 extern "C" void dpfs_attn_decode(const void* q, long long ldq, const void* kc, const void* vc, const int* len_ptr,
                                  void* o, long long ldo, float* part, int B, int H, int HD, int Tmax, float scale,
                                  hipStream_t s) {
-  const int ns = dpfs_decode_nsplit(Tmax);
-  const dim3 grid(ns, B * H);
-  if (HD == 32) {
-    attn_decode_split_k<32><<<grid, 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, len_ptr, H,
-                                                  Tmax, scale, part);
-    attn_decode_combine_k<32><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
-  } else if (HD == 64) {
-    attn_decode_split_k<64><<<grid, 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, len_ptr, H,
-                                                  Tmax, scale, part);
-    attn_decode_combine_k<64><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
-  } else {
-    attn_decode_split_k<128><<<grid, 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, len_ptr, H,
-                                                   Tmax, scale, part);
-    attn_decode_combine_k<128><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
-  }
+  attn_decode_hd<false>(q, ldq, kc, vc, len_ptr, o, ldo, part, B, H, HD, Tmax, scale, s);
+}
+
+extern "C" void dpfs_attn_decode_rows(const void* q, long long ldq, const void* kc, const void* vc, const int* len,
+                                      void* o, long long ldo, float* part, int B, int H, int HD, int Tmax, float scale,
+                                      hipStream_t s) {
+  attn_decode_hd<true>(q, ldq, kc, vc, len, o, ldo, part, B, H, HD, Tmax, scale, s);
 }
 
 extern "C" void dpfs_kv_append(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc,
                                const int* len_ptr, int B, int H, int HD, int Tmax, hipStream_t s) {
   const int n = 2 * B * H * HD / 8;
-  kv_append_k<<<(n + 255) / 256, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kc, (bf16*)vc,
-                                              len_ptr, B, H, HD, Tmax);
+  kv_append_k<false><<<(n + 255) / 256, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kc, (bf16*)vc,
+                                                     len_ptr, B, H, HD, Tmax);
+}
+
+extern "C" void dpfs_kv_append_rows(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc,
+                                    const int* len, int B, int H, int HD, int Tmax, hipStream_t s) {
+  const int n = 2 * B * H * HD / 8;
+  kv_append_k<true><<<(n + 255) / 256, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kc, (bf16*)vc,
+                                                    len, B, H, HD, Tmax);
 }
 
 extern "C" void dpfs_step_advance(int* len_ptr, int64_t* pos, int B, hipStream_t s) {
   step_advance_k<<<1, 64, 0, s>>>(len_ptr, pos, B);
+}
+
+extern "C" void dpfs_step_advance_rows(int* len, int64_t* pos, int B, int t_max, hipStream_t s) {
+  step_advance_rows_k<<<(B + 255) / 256, 256, 0, s>>>(len, pos, B, t_max);
 }
 
 extern "C" int dpfs_gemv16_ok(int M, int N, int K, long long lda, long long ldw) {
@@ -368,5 +423,12 @@ extern "C" void dpfs_rope_append(void* qkv, long long ld, const int64_t* pos, co
                                  const int* len_ptr, int B, int H, int HD, int Tmax, hipStream_t s) {
   const int total = B * 2 * H * (HD / 16) + B * H * HD / 8;
   const int grid = (total + 255) / 256;
-  rope_append_k<<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (bf16*)kc, (bf16*)vc, len_ptr, B, H, HD, Tmax);
+  rope_append_k<false><<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (bf16*)kc, (bf16*)vc, len_ptr, B, H, HD, Tmax);
+}
+
+extern "C" void dpfs_rope_append_rows(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kc, void* vc,
+                                      const int* len, int B, int H, int HD, int Tmax, hipStream_t s) {
+  const int total = B * 2 * H * (HD / 16) + B * H * HD / 8;
+  const int grid = (total + 255) / 256;
+  rope_append_k<true><<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (bf16*)kc, (bf16*)vc, len, B, H, HD, Tmax);
 }

@@ -11,7 +11,9 @@ Fixed reference bugs: the decode loads ``ckpt_paths[-1]`` (the
 indexes the last *character* of a path string, ``test.py:124``), and the embedding no longer
 mutates the token buffer, so TP>1 decoding is correct.  Extensions: ``--synthetic_prompts``
 (token-id prompts when no tokenizer file is available), the vocab-parallel loss, and sampled
-decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily).
+decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily), and
+``--decode_batch N``: the prompts are decoded N at a time as one ragged batch (per-row KV
+lengths, ``models/generation.py``) instead of one by one.
 """
 from __future__ import annotations
 
@@ -70,6 +72,8 @@ def get_test_args(argv=None):
     g.add_argument("--top_k", type=int, default=0, help="sample from the k largest logits (0: off)")
     g.add_argument("--top_p", type=float, default=1.0, help="sample from the top-p nucleus (1: off)")
     g.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling draws")
+    g.add_argument("--decode_batch", type=int, default=1,
+                   help="prompts decoded together as one ragged batch (1: one by one, the reference)")
     g = p.add_argument_group("other")
     g.add_argument("--random_seed", type=int, default=0)
     g.add_argument("--device", type=str, default=None)
@@ -125,6 +129,46 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
             return out.tolist()
 
 
+@torch.inference_mode()
+def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
+                        top_k: int = 0, top_p: float = 1.0, seed: int = 0):
+    """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
+    batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
+    reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
+    (``seed``, b, position)."""
+    from .models.generation import generate
+    prompts = [list(p) for p in prompts]
+    if not prompts:
+        return []
+    lens = [1 + len(p) for p in prompts]
+    if max(lens) > max_len:   # such a prompt still gets its one token (greedy_decode): one by one
+        return [greedy_decode(model, p, bos, eos, max_len, dev, True, temperature, top_k, top_p, seed) for p in prompts]
+    tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
+    for b, p in enumerate(prompts):
+        tokens[b, :lens[b]] = torch.tensor([bos] + p, dtype=torch.long, device=dev)
+    outs = generate(model, tokens, max_new_tokens=max_len + 1 - min(lens), eos_id=eos, max_len=max_len + 1,
+                    temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, prompt_lens=lens)
+    res = []
+    for p, out in zip(prompts, outs):
+        out = out[1:]
+        if out and out[-1] == eos and len(out) > len(p):
+            out = out[:-1]
+        res.append(out)
+    return res
+
+
+def _decode_all(model, prompts, ds, args, dev, sampling):
+    """Continuations of ``prompts`` (lists of ids): one by one, or ``--decode_batch`` at a time."""
+    n = args.decode_batch
+    if n <= 1:
+        return [greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
+                for ids in prompts]
+    outs = []
+    for i in range(0, len(prompts), n):
+        outs += greedy_decode_batch(model, prompts[i:i + n], ds.bos, ds.eos, args.max_decode_len, dev, **sampling)
+    return outs
+
+
 def test(rank, args):
     set_seed(args.random_seed)
     use_cuda = (args.device or ("cuda" if torch.cuda.is_available() else "cpu")) == "cuda"
@@ -164,20 +208,17 @@ def test(rank, args):
     sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.sample_seed)
     decoded = []
     if args.synthetic_prompts or not args.tokenizer_path:
-        for i in range(4):
-            g = torch.Generator().manual_seed(i)
-            ids = torch.randint(3, margs.vocab_size, (8,), generator=g).tolist()
-            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
+        prompts = [torch.randint(3, margs.vocab_size, (8,), generator=torch.Generator().manual_seed(i)).tolist()
+                   for i in range(4)]
+        for ids, out in zip(prompts, _decode_all(model, prompts, ds, args, dev, sampling)):
             assert out[:len(ids)] == ids
             decoded.append((str(ids), str(out[len(ids):])))
     else:
         from tokenizers import Tokenizer
         tok = Tokenizer.from_file(args.tokenizer_path)
         assert tok.token_to_id(BOS_TOKEN) == ds.bos and tok.token_to_id(EOS_TOKEN) == ds.eos
-        for t in PROMPTS:
-            t = t.strip()
-            ids = tok.encode(t).ids
-            out = greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
+        texts = [t.strip() for t in PROMPTS]
+        for t, out in zip(texts, _decode_all(model, [tok.encode(t).ids for t in texts], ds, args, dev, sampling)):
             text = tok.decode(out).strip()
             decoded.append((t, text[len(t):] if text.startswith(t) else text))
     with open(save_path, "a") as fp:
@@ -195,6 +236,8 @@ def main(argv=None):
     args = get_test_args(argv)
     if args.no_kv_cache and args.temperature != 0:
         raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
+    if args.decode_batch < 1 or (args.decode_batch > 1 and args.no_kv_cache):
+        raise ValueError("--decode_batch must be >= 1, and > 1 batches the KV-cached decode step: drop --no_kv_cache")
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)
     mp.spawn(test, args=(args,), nprocs=args.tp_size, join=True)

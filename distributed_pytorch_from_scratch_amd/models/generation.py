@@ -20,6 +20,14 @@ The token choice is ``argmax`` (greedy, the default) or, with ``temperature > 0`
 ``sample_logits`` launch (csrc/kernels/sample.hip: temperature, top-k, top-p, a stateless
 Philox draw keyed on (seed, row, position)) inside the same captured step.
 
+Ragged batches (``generate(..., prompt_lens=...)``): the prompts of a batch may differ in
+length.  The prompt is right-padded; ``cache.len_t`` then holds one int32 per sequence and the
+decode kernels read ``len_t[b]`` (their per-row forms), every row appends at its own length and
+carries its own position, and the per-row step advance (``_step_advance_rows``) clamps a row
+that fills the cache (it is frozen: appends nothing, reads only its cache rows) while shorter
+rows go on.  The lengths are device data like the positions, so one captured graph serves every
+mix of prompt lengths of the same ``(B, t_max)``.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -48,15 +56,49 @@ from ..parallel import tp_comm
 class KVCache:
     """Per-layer key/value buffers ``(B, T_max, H_local, hd)`` in the activation dtype."""
 
-    def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device):
+    def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
+                 ragged: bool = False):
         self.k = [torch.empty(B, t_max, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.empty(B, t_max, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
-        self.len = 0                      # host view (prefill / multi-token steps)
-        self.len_t = torch.zeros(1, dtype=torch.int32, device=device)   # device view (decode steps)
+        self.len = 0                      # host view (prefill / multi-token steps); ragged: the longest row
+        # device view (decode steps): one length for the batch, or with ``ragged`` one per row
+        self.len_t = torch.zeros(B if ragged else 1, dtype=torch.int32, device=device)
+        self.lens = [0] * B if ragged else None   # host view of the per-row lengths
         self.t_max = t_max
 
+    @property
+    def ragged(self) -> bool:
+        return self.lens is not None
+
+    def reset(self):
+        self.len = 0
+        if self.ragged:
+            self.lens = [0] * len(self.lens)
+
+    def set_lens(self, lens):
+        self.lens = [min(int(n), self.t_max) for n in lens]
+        self.len = max(self.lens)
+
+    def advance(self, n: int = 1):
+        """Host bookkeeping of ``n`` decode steps (what ``step_advance`` did on the device)."""
+        if self.ragged:
+            self.set_lens(m + n for m in self.lens)
+        else:
+            self.len += n
+
     def sync_device_len(self):
-        self.len_t.fill_(self.len)
+        if self.ragged:
+            self.len_t.copy_(torch.tensor(self.lens, dtype=torch.int32))
+        else:
+            self.len_t.fill_(self.len)
+
+    def device_pos(self) -> torch.Tensor:
+        """Position ids (B,) int64 of the next token of every row, from the device lengths (a
+        full row of a ragged cache stays on the cache's last position)."""
+        B = self.k[0].size(0)
+        if self.ragged:
+            return self.len_t.clamp(max=self.t_max - 1).long()
+        return self.len_t.long().expand(B).contiguous()
 
 
 def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int, T: int):
@@ -89,18 +131,38 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
     return attn.wo(o.reshape(B * T, h * hd))
 
 
+def _check_lens(lens, B: int, T: int) -> List[int]:
+    lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    if len(lens) != B:
+        raise ValueError(f"prompt_lens: need one length per sequence ({B}), got {len(lens)}")
+    if any(n < 1 or n > T for n in lens):
+        raise ValueError(f"prompt_lens: every length must be in [1, {T}], got {lens}")
+    return lens
+
+
 @torch.inference_mode()
-def logits_step(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
-    """Feed ``ids`` (B, T) at positions cache.len.., return (B, vocab) logits of the last one."""
+def logits_step(model, ids: torch.Tensor, cache: KVCache, lens=None) -> torch.Tensor:
+    """Feed ``ids`` (B, T) at positions cache.len.., return (B, vocab) logits of the last one.
+
+    ``lens`` (B ints in [1, T]) prefills a ragged cache with a right-padded prompt: row b holds
+    ``lens[b]`` real ids, the logits are those of its last real id, and its cache length becomes
+    ``lens[b]`` (the cache rows of the padding are overwritten by the appends before any read).
+    Later single-token steps on that cache advance every row at its own length."""
     B, T = ids.shape
     dev = ids.device
     dt = model.act_dtype(dev)
+    if lens is not None:
+        if not cache.ragged:
+            raise ValueError("logits_step: lens needs a KVCache(..., ragged=True)")
+        lens = _check_lens(lens, B, T)
+    if cache.ragged and T > 1 and cache.len > 0:
+        raise ValueError("logits_step: a multi-token continuation of a ragged cache is not supported")
     assert cache.len + T <= cache.t_max <= model.args.maxlen
     if T == 1 and cache.len > 0:
         cache.sync_device_len()
-        pos = torch.full((B,), cache.len, dtype=torch.int64, device=dev)
+        pos = cache.device_pos() if cache.ragged else torch.full((B,), cache.len, dtype=torch.int64, device=dev)
         _, logits = decode_step(model, ids, pos, cache)
-        cache.len += 1
+        cache.advance()
         return logits
     model.embedding.out_dtype = dt
     x = model.embedding(ids).reshape(B * T, -1).to(dt)
@@ -109,8 +171,13 @@ def logits_step(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     for li, layer in enumerate(model.layers):
         x = x + _attention_step(layer, layer.norm1(x), positions, tab, cache, li, B, T)
         x = x + layer.ffn(layer.norm2(x))
-    cache.len += T
-    h = model.norm(x.view(B, T, -1)[:, -1].contiguous())
+    if cache.ragged:
+        cache.set_lens(lens if lens is not None else [T] * B)
+        last = torch.tensor(cache.lens, device=dev) - 1       # the last real id of every row
+        h = model.norm(x.view(B, T, -1)[torch.arange(B, device=dev), last].contiguous())
+    else:
+        cache.len += T
+        h = model.norm(x.view(B, T, -1)[:, -1].contiguous())
     logits = model._lm_head_local(h)
     logits = comm_ops.Gather.apply(logits, model.lm_head.sizes)
     return logits[..., : model.vocab_size].float()
@@ -131,7 +198,8 @@ def _pick(model, logits: torch.Tensor, pos: torch.Tensor, sample):
 
 def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sample=None):
     """One token per sequence (``ids`` (B, 1), ``pos`` (B,) int64 = cache.len_t) against the
-    cache; advances ``cache.len_t`` and ``pos`` on the device.  Returns (next ids (B,),
+    cache; advances ``cache.len_t`` and ``pos`` on the device (a ragged cache: per row, clamped
+    at the cache capacity).  Returns (next ids (B,),
     logits (B, vocab) fp32); the ids are the ``argmax``, or with ``sample`` = (temperature,
     top_k, top_p, seed) a draw keyed on (seed, row, ``pos``).  Touches no host state:
     graph-capturable."""
@@ -178,8 +246,15 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     _, hfin, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, model.norm.scale, model.norm.eps)
     logits = proj(hfin, W(model.lm_head.weight), model.lm_head.bias)
     nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
-    K(pos).step_advance(cache.len_t, pos)
+    _advance(cache, pos)
     return nxt, logits
+
+
+def _advance(cache: KVCache, pos: torch.Tensor) -> None:
+    if cache.ragged:
+        K(pos)._step_advance_rows(cache.len_t, pos, cache.t_max)
+    else:
+        K(pos).step_advance(cache.len_t, pos)
 
 
 def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sample=None):
@@ -201,7 +276,7 @@ def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVC
         x = x + layer.ffn(layer.norm2(x))
     logits = model._lm_head_local(model.norm(x))
     nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
-    K(pos).step_advance(cache.len_t, pos)
+    _advance(cache, pos)
     return nxt, logits
 
 
@@ -227,7 +302,7 @@ class DecodeGraph:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self.pos.copy_(cache.len_t.long().expand(B))
+            self.pos.copy_(cache.device_pos())
             decode_step(model, self.ids, self.pos, cache, sample)
         torch.cuda.current_stream().wait_stream(s)
         cache.len_t.copy_(saved)
@@ -276,24 +351,26 @@ def _use_graph(dev) -> bool:
             and (p is None or p.tp_size == 1))
 
 
-_SESSIONS = {}   # (id(model), B, t_max, device) -> KV cache + captured decode graphs
+_SESSIONS = {}   # (id(model), B, t_max, device, ragged) -> KV cache + captured decode graphs
 
 
-def _session(model, B: int, t_max: int, dev):
-    """The KV cache and decode graphs for this (model, batch, length): reused by the next
-    generate() call of the same shape, so serving pays the graph capture once.  Reused only
+def _session(model, B: int, t_max: int, dev, ragged: bool = False):
+    """The KV cache and decode graphs for this (model, batch, length, uniform / ragged): reused
+    by the next generate() call of the same shape, so serving pays the graph capture once (a
+    ragged session serves every mix of prompt lengths: they are device data).  Reused only
     while it is the same live model object and no parameter changed since the capture (the
     graphs hold the bf16 weight copies of that version); otherwise rebuilt.  One kept shape
     per model, and only caches up to DPFS_DECODE_SESSION_MAX_GB (default 16) are kept;
     ``clear_sessions()`` frees them."""
     attn0 = model.layers[0].attn
-    key = (id(model), B, t_max, str(dev))
+    key = (id(model), B, t_max, str(dev), ragged)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
-        ent["cache"].len = 0
+        ent["cache"].reset()
         return ent["cache"], ent["graphs"]
-    cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev)
+    cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev,
+                    ragged)
     graphs = {}
     kv_bytes = sum(t.numel() * t.element_size() for t in cache.k + cache.v)
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
@@ -312,10 +389,17 @@ def clear_sessions():
 @torch.inference_mode()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
              max_len: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-             seed: int = 0) -> List[List[int]]:
+             seed: int = 0, prompt_lens=None) -> List[List[int]]:
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
+
+    ``prompt_lens`` (B ints in [1, T0], a sequence or a tensor) decodes a ragged batch: row b of
+    the right-padded ``prompt`` holds ``prompt_lens[b]`` real ids (the padding values do not
+    matter), and the result is ``prompt[b, :prompt_lens[b]]`` plus that row's generated ids.  A
+    row stops after ``eos_id``, after ``max_new_tokens`` new ids or when its own total reaches
+    ``max_len``; generation ends when every row has stopped.  This always runs the per-row decode
+    kernels, also when all lengths are equal.
 
     ``temperature`` 0 decodes greedily.  ``temperature`` > 0 samples every token with
     ``sample_logits``: softmax(logits / temperature) cut to the ``top_k`` largest logits (0:
@@ -328,6 +412,9 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
     B, T0 = prompt.shape
     dev = prompt.device
+    if prompt_lens is not None:
+        return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
+                                sample)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev)
     out = [list(map(int, row)) for row in prompt.tolist()]
@@ -379,5 +466,73 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         else:
             nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
             cache.len += 1
+            if emit(nxt.tolist()):
+                return out
+
+
+def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample):
+    """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
+    step, finished or not; the host drops the ids of a finished row, and the device keeps a row
+    that has filled the cache frozen inside it (``_step_advance_rows``)."""
+    B = prompt.size(0)
+    dev = prompt.device
+    cap = min(model.args.maxlen, max_len or model.args.maxlen)     # total length at which a row stops
+    t_max = min(cap, max(lens) + max_new_tokens)
+    cache, graphs = _session(model, B, t_max, dev, ragged=True)
+    rows = prompt.tolist()
+    out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
+    done = [n >= cap for n in lens]
+    if max_new_tokens <= 0 or all(done):
+        return out
+    # The padded prompt up to the longest row that fits the cache; a row at or past the cache
+    # capacity is done already and enters the cache full (frozen).
+    T = min(max(lens), t_max)
+    logits = logits_step(model, prompt[:, :T].contiguous(), cache, [min(n, T) for n in lens])
+    if sample is None:
+        nxt = logits.argmax(-1)
+    else:   # the first token of row b follows position lens[b] - 1
+        pos0 = torch.tensor(cache.lens, dtype=torch.int64, device=dev) - 1
+        nxt = K(logits).sample_logits(logits, model.vocab_size, *sample, pos0)[0]
+    cache.sync_device_len()
+    pos = cache.device_pos()
+    chunk = _GRAPH_STEPS
+    n_gen = 0
+
+    def emit(row) -> bool:
+        """Append one step's ids to the live rows; True when every row is finished."""
+        nonlocal n_gen
+        n_gen += 1
+        for b, t in enumerate(row):
+            if not done[b]:
+                out[b].append(int(t))
+                done[b] = (eos_id is not None and int(t) == eos_id) or len(out[b]) >= cap
+        return all(done) or n_gen >= max_new_tokens
+
+    if emit(nxt.tolist()):
+        return out
+    while True:
+        if _use_graph(dev):
+            # S steps per replay while S more tokens are wanted and the longest live row has room
+            # for them (a finished row may run past its end: the kernels keep it in bounds)
+            longest = max(n for n, d in zip(cache.lens, done) if not d)
+            S = chunk if (max_new_tokens - n_gen >= chunk and longest + chunk <= t_max) else 1
+            gkey = S if sample is None else (S, sample)
+            g = graphs.get(gkey)
+            if g is None:
+                if sample is not None and len(graphs) >= _MAX_GRAPHS:
+                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != sample]:
+                        del graphs[k]     # sampling graphs of earlier settings; greedy ones stay
+                g = graphs[gkey] = DecodeGraph(model, cache, B, S, sample)
+            g.pos.copy_(cache.device_pos())
+            outs = g.step(nxt)
+            steps = outs.tolist()
+            nxt = g.out
+            for row in steps:
+                cache.advance()
+                if emit(row):
+                    return out
+        else:
+            nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
+            cache.advance()
             if emit(nxt.tolist()):
                 return out

@@ -97,6 +97,7 @@ attn_decode = reference.attn_decode
 kv_append = reference.kv_append
 rope_append = reference.rope_append
 step_advance = reference.step_advance
+_step_advance_rows = reference._step_advance_rows
 gemv_nt = reference.gemv_nt
 
 

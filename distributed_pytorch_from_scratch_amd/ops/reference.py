@@ -204,8 +204,13 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, len: torch.Tensor,
                 scale: float) -> torch.Tensor:
     """One query row per (sequence, head) against cache rows [0, len]: q [B, >= H*hd] rows,
-    caches (B, T_max, H, hd), len a 1-element int tensor.  Returns o [B, H*hd] in q.dtype."""
-    B, _, H, hd = k_cache.shape
+    caches (B, T_max, H, hd), len a 1-element int tensor, or one of B elements (sequence b
+    attends rows [0, min(len[b] + 1, T_max))).  Returns o [B, H*hd] in q.dtype."""
+    B, Tmax, H, hd = k_cache.shape
+    if len.numel() != 1:
+        assert len.numel() == B, "len must have 1 or B elements"
+        return torch.cat([attn_decode(q[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1],
+                                      len.reshape(-1)[b:b + 1].clamp(max=Tmax - 1), scale) for b in range(B)])
     L = int(len.reshape(-1)[0]) + 1
     qf = q[:, : H * hd].float().view(B, H, 1, hd)
     kf = k_cache[:, :L].float().transpose(1, 2)          # B H L hd
@@ -215,8 +220,15 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
 
 
 def kv_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, len: torch.Tensor) -> None:
-    """cache[:, len] = the k / v parts of the packed qkv rows [B, 3*H*hd]."""
-    B, _, H, hd = k_cache.shape
+    """cache[:, len] = the k / v parts of the packed qkv rows [B, 3*H*hd]; with a B-element
+    len, cache[b, len[b]], and a full row (len[b] >= T_max) appends nothing."""
+    B, Tmax, H, hd = k_cache.shape
+    if len.numel() != 1:
+        assert len.numel() == B, "len must have 1 or B elements"
+        for b, t in enumerate(len.reshape(-1).tolist()):
+            if 0 <= t < Tmax:
+                kv_append(qkv[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1], len.reshape(-1)[b:b + 1])
+        return
     t = int(len.reshape(-1)[0])
     k_cache[:, t] = qkv[:, H * hd: 2 * H * hd].view(B, H, hd).to(k_cache.dtype)
     v_cache[:, t] = qkv[:, 2 * H * hd: 3 * H * hd].view(B, H, hd).to(v_cache.dtype)
@@ -251,8 +263,20 @@ def rope_append(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_cac
 
 
 def step_advance(len: torch.Tensor, pos: torch.Tensor) -> None:
+    """End of a decode step, one length for the batch: len += 1, pos[:] = len."""
+    assert len.numel() == 1, "per-row lengths: _step_advance_rows(len, pos, t_max)"
     len += 1
     pos.fill_(int(len.reshape(-1)[0]))
+
+
+def _step_advance_rows(len: torch.Tensor, pos: torch.Tensor, t_max: int) -> None:
+    """End of a decode step with one length per sequence: len[b] = min(len[b] + 1, t_max),
+    pos[b] = min(len[b], t_max - 1), so a row that fills its cache (capacity ``t_max``) is frozen
+    there.  (The leading underscore follows the native module, whose recorded public surface
+    keeps the two-argument ``step_advance``.)"""
+    assert len.numel() == pos.numel(), "len must have one element per pos entry"
+    len.copy_((len + 1).clamp(max=t_max))
+    pos.copy_(len.reshape(pos.shape).clamp(max=t_max - 1))
 
 
 # ----------------------------------------------------------------------- sampling ----

@@ -3,12 +3,20 @@ reference's full recompute per token (test.py:144-150), one GPU.
 
     python tools/decode_bench.py [--model gpt2-small] [--batch 1 8] [--prompt 128] [--new 256]
                                  [--temperature T --top_k K --top_p P] [--repeats R] [--sample-kernel]
+                                 [--ragged | --ragged-equal]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
 (``sample_logits`` in place of ``argmax``; the full-recompute baseline is then skipped);
 ``--repeats`` times each (batch, mode) that many times; ``--sample-kernel`` times the
 ``sample_logits`` launch alone on bf16 rows of the model's padded vocabulary.
+
+``--ragged`` decodes a ragged batch (``generate(..., prompt_lens=...)``, the per-row decode
+kernels): the prompt lengths of a batch are spread evenly over [prompt/4, prompt] (row b of B:
+``prompt/4 + b (prompt - prompt/4) / (B - 1)``), every row generates ``--new`` ids, and a
+"one-by-one" line times the same prompts decoded one after the other at batch 1 (uniform path,
+each with its session warm).  ``--ragged-equal`` runs the per-row path with every length =
+``--prompt``: against the plain run, the price of the per-row length loads.
 """
 from __future__ import annotations
 
@@ -34,6 +42,8 @@ def main():
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--sample-kernel", action="store_true", help="time the sample_logits launch alone")
+    ap.add_argument("--ragged", action="store_true", help="ragged batch: lengths spread over [prompt/4, prompt]")
+    ap.add_argument("--ragged-equal", action="store_true", help="per-row path with all lengths = prompt")
     a = ap.parse_args()
     sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
     import torch
@@ -51,22 +61,49 @@ def main():
         return sample_kernel_bench(a, m.lm_head.weight.size(0), args.vocab_size)
     for B in a.batch:
         prompt = torch.randint(0, args.vocab_size, (B, a.prompt), device="cuda")
+        lens = None
+        if a.ragged:
+            lo = max(1, a.prompt // 4)
+            lens = [lo + b * (a.prompt - lo) // max(1, B - 1) for b in range(B)] if B > 1 else [a.prompt]
+        elif a.ragged_equal:
+            lens = [a.prompt] * B
+        kw = dict(sampling, prompt_lens=lens) if lens else sampling
         for mode in ("graph", "eager"):
             os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
-            generate(m, prompt, max_new_tokens=a.new, **sampling)   # warm-up: GEMM choices, graph capture
+            generate(m, prompt, max_new_tokens=a.new, **kw)         # warm-up: GEMM choices, graph capture
                                                                     #   (reused by the same-shape call)
             for _ in range(a.repeats):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                generate(m, prompt, max_new_tokens=a.new, **sampling)
+                generate(m, prompt, max_new_tokens=a.new, **kw)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 rec = {"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
                        "ms_per_step": round(1000 * dt / a.new, 3), "tokens_per_s": round(B * a.new / dt, 1)}
+                if lens:
+                    rec.update(ragged="spread" if a.ragged else "equal", min_len=min(lens), max_len=max(lens))
                 if a.temperature > 0:
                     rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
                 print(json.dumps(rec), flush=True)
-        if a.temperature > 0:
+        if a.ragged and B > 1:
+            # the same prompts one after the other at batch 1 (uniform path, graph), each timed
+            # right after its own warm-up call, so no capture is in the time
+            os.environ["DPFS_DECODE_GRAPH"] = "1"
+            for _ in range(a.repeats):
+                dt = 0.0
+                for b in range(B):
+                    row = prompt[b:b + 1, :lens[b]].contiguous()
+                    generate(m, row, max_new_tokens=a.new, **sampling)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    generate(m, row, max_new_tokens=a.new, **sampling)
+                    torch.cuda.synchronize()
+                    dt += time.perf_counter() - t0
+                print(json.dumps({"model": a.model, "batch": B, "mode": "one-by-one", "prompt": a.prompt, "new": a.new,
+                                  "ragged": "spread", "min_len": min(lens), "max_len": max(lens),
+                                  "ms_per_step": round(1000 * dt / (B * a.new), 3),
+                                  "tokens_per_s": round(B * a.new / dt, 1)}), flush=True)
+        if a.temperature > 0 or lens:
             continue
         # reference formulation: every token re-runs the whole prefix (no cache)
         seq = prompt
