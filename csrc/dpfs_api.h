@@ -178,14 +178,35 @@ bool dpfs_gemm4_nn_swiglu_bwd(const void* A, const void* B, const void* gu, void
                               int K, int lda, int ldb, int ldgu, int lddgu, int perm, unsigned a_bytes,
                               unsigned b_bytes, hipStream_t s);
 long long dpfs_gemm4_sk_ws(int M, int N, int K);
-void dpfs_gemm4_set_sk_ws(float* p, long long n);
 int dpfs_gemm4_sk_error(int reset);
 void dpfs_gemm4_sk_starve(int on);
-bool dpfs_gemm4_launch(int layout, int out_f32, const void* A, const void* B, void* C, const float* bias, int M,
-                       int N, int K, int lda, int ldb, int ldc, int kps, int splits, long long slab_stride,
-                       unsigned a_bytes, unsigned b_bytes, const int64_t* rope_pos, const float* rope_tab,
-                       int rope_cols, int rope_hd, const void* A2, const void* B2, int k_switch, int lda2, int ldb2,
-                       unsigned a2_bytes, unsigned b2_bytes, int bn_force, hipStream_t s);
+// One v4 GEMM.  Zero-initialised (`dpfs_gemm4_args a{}`) means: no RoPE, no second buffer, tile
+// width chosen per shape, plain stores, no stream-K; a caller sets the fields it uses by name.
+struct dpfs_gemm4_args {
+  int layout;    // 0 = NT, 1 = NN, 2 = TN
+  int out_f32;   // C: 0 = bf16, 1 = fp32 (split-K slabs)
+  const void* A;
+  const void* B;
+  void* C;
+  const float* bias;
+  int M, N, K, lda, ldb, ldc;
+  int kps, splits;         // rows of K per split (a multiple of 32), number of splits
+  long long slab_stride;   // elements between the splits' slabs
+  unsigned a_bytes, b_bytes;
+  const int64_t* rope_pos;   // RoPE in the epilogue where rope_cols > 0 (bf16 NT)
+  const float* rope_tab;
+  int rope_cols, rope_hd;
+  const void* A2;   // rows of K from k_switch on come from second buffers (null: one buffer)
+  const void* B2;
+  int k_switch, lda2, ldb2;
+  unsigned a2_bytes, b2_bytes;
+  int width;           // tile width of a non-split bf16 GEMM: 0 = per shape, 256 / 192 forced
+  int stream_stores;   // the bf16 output written with non-temporal stores (plain NT / NN)
+  int stream_k;        // the stream-K kernel where it applies (dpfs_gemm4_sk_ws)
+  float* sk_ws;        // stream-K partials / flags: dpfs_gemm4_sk_ws floats
+  long long sk_ws_floats;
+};
+bool dpfs_gemm4_launch(const dpfs_gemm4_args* args, hipStream_t s);
 long long dpfs_gemm_tn_group_ws(int n, const int* M, const int* N, const int* lda, const int* ldb, int K,
                                 const int* acc, const int* lda2, const int* ldb2, int K1);
 int dpfs_gemm_tn_group(int n, const void* const* A, const void* const* B, float* const* C, const int* M, const int* N,

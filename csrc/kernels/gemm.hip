@@ -907,15 +907,28 @@ static void dpfs_rope_after_gemm(void* C, RopeArgs r, int M, int ldc, hipStream_
 // v4 is dpfs_gemm4_launch (csrc/kernels/gemm4.hip: one wave per SIMD, 128 x 128 per wave).
 // Per-call kernel variant (an argument of every GEMM entry point, never process state):
 //   0 = v4 with its per-shape tile width (the default for every layout),
-//   1 / 2 = v4 with the 256 / 192 tile width forced (non-split bf16 NT / NN),
+//   1 / 2 = v4 with the 256 / 192 tile width forced (non-split bf16 NT / NN; 1 in fact runs
+//   as 4, see bf16_gemm),
 //   3 = the v3 kernel (8 waves, 128 x 64 per wave);
 //   + 4 (variants 4 / 5 / 6): the v4 bf16 output written with non-temporal (streaming)
 //   stores, so the output does not displace the operands in L2 (plain NT / NN only).
 // Where the v4 launcher declines a shape (32-bit spans, alignment) the v3 kernel runs.
 static bool use_v4(int variant) { return g_gemm_impl >= 3 && (variant & 3) != 3; }
-static int v4_bn(int variant) {
-  const int w = variant & 3;
-  return (w == 1 ? 256 : (w == 2 ? 192 : 0)) | ((variant & 4) ? 0x100 : 0) | ((variant & 8) ? 0x200 : 0);
+// The operands of a v4 launch; the caller names everything else it uses (dpfs_gemm4_args).
+static dpfs_gemm4_args v4_operands(int layout, const void* A, const void* B, int M, int N, int K, int lda, int ldb,
+                                   unsigned a_bytes, unsigned b_bytes) {
+  dpfs_gemm4_args g{};
+  g.layout = layout;
+  g.A = A;
+  g.B = B;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = lda;
+  g.ldb = ldb;
+  g.a_bytes = a_bytes;
+  g.b_bytes = b_bytes;
+  return g;
 }
 
 extern "C" long long dpfs_gemm_bf16_ws(int M, int N, int K) {
@@ -932,13 +945,17 @@ static void bf16_gemm(const void* A, const void* B, void* C, const float* bias, 
   // 256 x 256 tiles are 1.5 per CU, e.g. the lm_head data gradient)
   const bool sk = v4 && (variant & 8) && rope.cols == 0 && dpfs_gemm4_sk_ws(M, N, K) > 0;
   const int S = sk ? 1 : bf16_splits(M, N, K);
-  const int lay = BKM ? 0 : 1;
+  dpfs_gemm4_args g4 = v4_operands(BKM ? 0 : 1, A, B, M, N, K, lda, ldb, ab, bb);
   if (S > 1 && g_ws && g_ws_floats >= (long long)S * M * N) {
     int kps = (K + S - 1) / S;
     kps = ((kps + BKK - 1) / BKK) * BKK;
-    const bool done4 = v4 && dpfs_gemm4_launch(lay, 1, A, B, g_ws, nullptr, M, N, K, lda, ldb, N, kps, S,
-                                               (long long)M * N, ab, bb, nullptr, nullptr, 0, 64, nullptr, nullptr, 0,
-                                               0, 0, 0u, 0u, 0, s);
+    g4.out_f32 = 1;
+    g4.C = g_ws;
+    g4.ldc = N;
+    g4.kps = kps;
+    g4.splits = S;
+    g4.slab_stride = (long long)M * N;
+    const bool done4 = v4 && dpfs_gemm4_launch(&g4, s);
     if (!done4 && (g_gemm_impl != 3 || !launchp<true, BKM, 1>(pick_cfg(M, N, S), A, B, g_ws, nullptr, M, N, K, lda,
                                                                ldb, N, S, kps, (long long)M * N, ab, bb, s)))
       launch2<true, BKM, 1>(pick_cfg(M, N, S), A, B, g_ws, nullptr, M, N, K, lda, ldb, N, S, kps, (long long)M * N, ab,
@@ -949,12 +966,26 @@ static void bf16_gemm(const void* A, const void* B, void* C, const float* bias, 
     if (rope.cols > 0) dpfs_rope_after_gemm(C, rope, M, ldc, s);
     return;
   }
-  if (variant & 8) dpfs_gemm4_set_sk_ws(g_ws, g_ws_floats);   // (stream-K: its partials / flags)
-  const bool done4 = v4 && dpfs_gemm4_launch(lay, 0, A, B, C, bias, M, N, K, lda, ldb, ldc, ((K + 31) / 32) * 32, 1, 0,
-                                             ab, bb, rope.pos, rope.tab, rope.cols, rope.hd, nullptr, nullptr, 0, 0, 0,
-                                             0u, 0u, v4_bn(variant), s);
-  if (variant & 8) dpfs_gemm4_set_sk_ws(nullptr, 0);
-  if (done4) return;
+  g4.C = C;
+  g4.bias = bias;
+  g4.ldc = ldc;
+  g4.kps = ((K + 31) / 32) * 32;
+  g4.splits = 1;
+  g4.rope_pos = rope.pos;
+  g4.rope_tab = rope.tab;
+  g4.rope_cols = rope.cols;
+  g4.rope_hd = rope.hd;
+  // Variants 1 / 5 have never forced the 256 width: in the packed argument this replaces, 256
+  // was also the non-temporal-store bit (0x100), so both have always run as variant 4 (width
+  // per shape, non-temporal stores).  Kept as it was; the launcher itself honours width = 256.
+  g4.width = (variant & 3) == 2 ? 192 : 0;
+  g4.stream_stores = (variant & 4) != 0 || (variant & 3) == 1;
+  if (variant & 8) {   // (stream-K: its partials / flags in the split-K workspace)
+    g4.stream_k = 1;
+    g4.sk_ws = g_ws;
+    g4.sk_ws_floats = g_ws_floats;
+  }
+  if (v4 && dpfs_gemm4_launch(&g4, s)) return;
   if (rope.cols > 0 && rope.hd != 64) {   // v3's epilogue rotates 64-wide heads only
     bf16_gemm<BKM>(A, B, C, bias, M, N, K, lda, ldb, ldc, ab, bb, variant, s);
     dpfs_rope_after_gemm(C, rope, M, ldc, s);
@@ -1100,9 +1131,14 @@ extern "C" void dpfs_gemm_tn(const void* A, const void* B, float* C, float* ws, 
       int kps4 = (K + S4 - 1) / S4;
       kps4 = ((kps4 + BKK - 1) / BKK) * BKK;
       const bool direct4 = (S4 == 1 && !accumulate);
-      if (dpfs_gemm4_launch(2, 1, A, B, direct4 ? C : ws, nullptr, M, N, K, lda, ldb, N, direct4 ? ((K + 31) / 32) * 32 : kps4,
-                            S4, direct4 ? 0 : n, span_bytes(K, lda, M), span_bytes(K, ldb, N), nullptr, nullptr, 0, 64,
-                            nullptr, nullptr, 0, 0, 0, 0u, 0u, 0, s)) {
+      dpfs_gemm4_args g4 = v4_operands(2, A, B, M, N, K, lda, ldb, span_bytes(K, lda, M), span_bytes(K, ldb, N));
+      g4.out_f32 = 1;
+      g4.C = direct4 ? C : ws;
+      g4.ldc = N;
+      g4.kps = direct4 ? ((K + 31) / 32) * 32 : kps4;
+      g4.splits = S4;
+      g4.slab_stride = direct4 ? 0 : n;
+      if (dpfs_gemm4_launch(&g4, s)) {
         if (direct4) return;
         long long g = (n / 4 + 255) / 256;
         if (g > 4096) g = 4096;
@@ -1177,10 +1213,21 @@ extern "C" int dpfs_gemm_tn2(const void* A0, const void* B0, const void* A1, con
   const int K = K0 + K1;
   const long long n = (long long)M * N;
   const Dual d = {(const bf16*)A1, (const bf16*)B1, K0, lda1, ldb1, span_bytes(K1, lda1, M), span_bytes(K1, ldb1, N)};
-  const bool done4 = use_v4(variant) &&
-                     dpfs_gemm4_launch(2, 1, A0, B0, ws, nullptr, M, N, K, lda0, ldb0, N, kps, S, n,
-                                       span_bytes(K0, lda0, M), span_bytes(K0, ldb0, N), nullptr, nullptr, 0, 64, A1,
-                                       B1, K0, lda1, ldb1, d.a2_bytes, d.b2_bytes, 0, s);
+  dpfs_gemm4_args g4 = v4_operands(2, A0, B0, M, N, K, lda0, ldb0, span_bytes(K0, lda0, M), span_bytes(K0, ldb0, N));
+  g4.out_f32 = 1;
+  g4.C = ws;
+  g4.ldc = N;
+  g4.kps = kps;
+  g4.splits = S;
+  g4.slab_stride = n;
+  g4.A2 = A1;
+  g4.B2 = B1;
+  g4.k_switch = K0;
+  g4.lda2 = lda1;
+  g4.ldb2 = ldb1;
+  g4.a2_bytes = d.a2_bytes;
+  g4.b2_bytes = d.b2_bytes;
+  const bool done4 = use_v4(variant) && dpfs_gemm4_launch(&g4, s);
   if (!done4 && !launchp<false, false, 1>(cfg, A0, B0, ws, nullptr, M, N, K, lda0, ldb0, N, S, kps, n, span_bytes(K0, lda0, M),
                                 span_bytes(K0, ldb0, N), s, RopeArgs{nullptr, nullptr, 0}, d))
     return 0;

@@ -811,6 +811,12 @@ __device__ __forceinline__ void epilogue_swb(const Item& ci, int M, int F, const
   }
 }
 
+// ------------------------------------------------------------------------ kernel variants --
+// gemm4_k's template parameters, as the members of a variant type: Variant holds the
+// template's defaults, a layout (NT / NN / TN) the operand layouts, and the forms below
+// override what differs.  launch<V>() (below the kernel) is the one place that spells the
+// positional list; everything else names a variant.
+// AK / BKM: A / B K-major (else MN-major): NT = both, NN = A only, TN = neither.
 // OUT: 0 = bf16 C (+ fp32 bias[n], + RoPE); 1 = fp32 C / split-K slab.
 // DIAG: 0 = production; 1 / 2 = the timing builds (per-wave s_memtime split; 2 without DMA);
 // 3 = the ablation build that reads `dbg` (timing-only, tools/gemm4_probe.py): 4 = no DMA
@@ -839,6 +845,50 @@ __device__ __forceinline__ void epilogue_swb(const Item& ci, int M, int F, const
 // half the operand-register reads per FLOP, so the step's 32 transposed reads, 8 DMA pieces and
 // address / SALU work fit in the MFMA shadow (the 16x16x32 TN step issues ~1.5k cycles of
 // non-MFMA work against 1024 of matrix time).
+// SWB: the SwiGLU-backward epilogue (SwiBwd) with 1 or 2 gate / up row blocks in flight; 0 = none.
+// SA: 2 = the bf16 output written with non-temporal stores (streaming output), 0 = plain.
+// GRP: a group of TN GEMMs as one launch (TnGroup).  SK: stream-K (SkArgs).
+struct Variant {
+  static constexpr bool AK = true, BKM = true;
+  static constexpr int OUT = 0, DIAG = 0;
+  static constexpr bool FAST = false;
+  static constexpr int SCHED = 0, BN = 256, ROPE = 0;
+  static constexpr bool SWIGLU = false;
+  static constexpr int SWB = 0, BR = 0, SA = 0;
+  static constexpr bool M32 = false, GRP = false, SK = false;
+};
+struct NT : Variant {};
+struct NN : Variant { static constexpr bool BKM = false; };
+struct TN : Variant { static constexpr bool AK = false, BKM = false; };
+// The three main loops of a (layout, output): per-lane K checks (any K % 8); FAST with two
+// DMA pieces per MFMA row in rows 4-7; FAST with one piece per row (production), BR_ rows of
+// MFMAs ahead of the step's barrier.
+template <class L, int OUT_>
+struct Checked : L { static constexpr int OUT = OUT_; };
+template <class L, int OUT_>
+struct FastPaired : Checked<L, OUT_> { static constexpr bool FAST = true; };
+template <class L, int OUT_, int BR_ = 0>
+struct Fast : FastPaired<L, OUT_> { static constexpr int SCHED = 1, BR = BR_; };
+// What a form adds to a main loop.
+template <class V>
+struct Wide192 : V { static constexpr int BN = 192; };       // 256 x 192 tiles
+template <class V>
+struct StreamStores : V { static constexpr int SA = 2; };    // non-temporal bf16 stores
+template <class V>
+struct Mfma32 : V { static constexpr bool M32 = true; };     // the 32x32x16 main loop
+template <class V, int HD>
+struct Roped : V { static constexpr int ROPE = HD; };        // RoPE epilogue, head_dim HD
+template <class V, int D>
+struct Diag : V { static constexpr int DIAG = D; };          // timing (1, 2) / ablation (3) builds
+template <class V>
+struct StreamK : V { static constexpr bool SK = true; };
+struct SwigluFwd : Fast<NT, 0> { static constexpr bool SWIGLU = true; };
+template <int DEPTH>
+struct SwigluBwd : Fast<NN, 0> { static constexpr int SWB = DEPTH; };
+template <int BR_>
+struct TnGrouped : Mfma32<Fast<TN, 1, BR_>> { static constexpr bool GRP = true; };
+
+// (template parameters: documented at Variant above, which holds these defaults by name)
 template <bool AK, bool BKM, int OUT, int DIAG = 0, bool FAST = false, int SCHED = 0, int BN = 256, int ROPE = 0,
           bool SWIGLU = false, int SWB = 0, int BR = 0, int SA = 0, bool M32 = false, bool GRP = false,
           bool SK = false>
@@ -1362,38 +1412,80 @@ static int g4_cu_count() {
   return n[dev];
 }
 
-static int g_g4_group_m = 4;
-// Timing-only ablations (tools/gemm4_probe.py --ablate): bit 1 = output descriptor with zero
-// records (every store dropped), bit 2 = operand descriptors with zero records (every DMA
-// returns zeros, no memory traffic), 4 = no DMA wait, 8 = no step barrier (wrong results).
-// Bits 4 / 8 (and 1024: none) run the DIAG-3 build of the NT 256-wide kernel, the only one
-// that reads them.
-// Blocks of 4 MFMAs ahead of each step's wait + barrier in the 32x32x16 (TN weight-gradient)
-// main loop: 0 (default), 1, 2 (A/B hook).
-static int g_g4_br_tn = 0;
-extern "C" void dpfs_gemm4_br_tn(int v) { g_g4_br_tn = (v >= 0 && v <= 2) ? v : 0; }
-static int g_g4_ablate = 0;
-static unsigned long long* g_g4_diag = nullptr;   // [grid][4 waves][wait, body, epilogue, valid]
-extern "C" void dpfs_gemm4_ablate(int v) { g_g4_ablate = v; }
-extern "C" void dpfs_gemm4_diag(void* p) { g_g4_diag = (unsigned long long*)p; }
-// Main-loop variant (tools/gemm4_probe.py A/B): 0 = one DMA piece per MFMA row (default),
-// 1 = two pieces per row in rows 4-7; 2 = per-lane K checks even where FAST applies.
-static int g_g4_sched = 0;
-extern "C" void dpfs_gemm4_sched(int v) { g_g4_sched = v; }
-// Rows of MFMAs before each step's barrier (gemm4_k's BR) of the plain FAST kernels: 0, 1, 2.
-// 2 (default since the end of round 6): -0.18 ms per training step against 0 in 6 of 6
-// same-box interleaved rounds (profiles/r6_gemm_br_ab.txt); 1 is within 0.01 ms of 2.
-static int g_g4_br = 2;
-extern "C" void dpfs_gemm4_br(int v) { g_g4_br = (v >= 0 && v <= 2) ? v : 0; }
-extern "C" void dpfs_gemm4_group_m(int g) { g_g4_group_m = g > 0 ? g : 4; }
-// TN main loop: 1 = the 32x32x16 form (gemm4_k's M32, default), 0 = 16x16x32 (A/B probes).
-static int g_g4_m32 = 1;
-extern "C" void dpfs_gemm4_m32(int v) { g_g4_m32 = v ? 1 : 0; }
-// NN / NT main loop on 256-wide tiles: bit 0 = 32x32x16 for the fp32 (split-K) output, bit 1 =
-// for the bf16 (+ bias) output; 0 = 16x16x32 (default: the K-major 32x32x16 form measured
-// 0.3 ms/step slower in the GPT-2-small step, profiles/r5_m32k_ab.txt)
-static int g_g4_m32k = 0;
-extern "C" void dpfs_gemm4_m32k(int v) { g_g4_m32k = v & 3; }
+// A/B and probe knobs (process state; the Python names are ops.gemm4_*), defaults stated here.
+struct G4Knobs {
+  int group_m = 4;   // tile rows per group of the item order
+  // Blocks of 4 MFMAs ahead of each step's wait + barrier in the 32x32x16 (TN weight-gradient)
+  // main loop: 0 (default), 1, 2 (A/B hook).
+  int br_tn = 0;
+  // Timing-only ablations (tools/gemm4_probe.py --ablate): bit 1 = output descriptor with zero
+  // records (every store dropped), bit 2 = operand descriptors with zero records (every DMA
+  // returns zeros, no memory traffic), 4 = no DMA wait, 8 = no step barrier (wrong results).
+  // Bits 4 / 8 (and 1024: none) run the DIAG-3 build of the NT 256-wide kernel, the only one
+  // that reads them.
+  int ablate = 0;
+  unsigned long long* diag = nullptr;   // [grid][4 waves][wait, body, epilogue, valid]
+  // Main-loop variant (tools/gemm4_probe.py A/B): 0 = one DMA piece per MFMA row (default),
+  // 1 = two pieces per row in rows 4-7; 2 = per-lane K checks even where FAST applies.
+  int sched = 0;
+  // Rows of MFMAs before each step's barrier (Variant::BR) of the plain FAST kernels: 0, 1, 2.
+  // 2 (default since the end of round 6): -0.18 ms per training step against 0 in 6 of 6
+  // same-box interleaved rounds (profiles/r6_gemm_br_ab.txt); 1 is within 0.01 ms of 2.
+  int br = 2;
+  // TN main loop: 1 = the 32x32x16 form (Variant::M32, default), 0 = 16x16x32 (A/B probes).
+  int m32 = 1;
+  // NN / NT main loop on 256-wide tiles: bit 0 = 32x32x16 for the fp32 (split-K) output, bit 1 =
+  // for the bf16 (+ bias) output; 0 = 16x16x32 (default: the K-major 32x32x16 form measured
+  // 0.3 ms/step slower in the GPT-2-small step, profiles/r5_m32k_ab.txt)
+  int m32k = 0;
+  // gate / up row blocks in flight in the SWB epilogue (1 or 2; A/B hook, tools/ab_attr.py)
+  int swb_depth = 2;
+  // Test hook: the next stream-K launch runs its consumers with their producers' flags never
+  // set (the producers skip the flag store), so every consumer's wait times out.
+  int sk_starve = 0;
+};
+static G4Knobs g_knobs;
+extern "C" void dpfs_gemm4_group_m(int g) { g_knobs.group_m = g > 0 ? g : 4; }
+extern "C" void dpfs_gemm4_br_tn(int v) { g_knobs.br_tn = (v >= 0 && v <= 2) ? v : 0; }
+extern "C" void dpfs_gemm4_ablate(int v) { g_knobs.ablate = v; }
+extern "C" void dpfs_gemm4_diag(void* p) { g_knobs.diag = (unsigned long long*)p; }
+extern "C" void dpfs_gemm4_sched(int v) { g_knobs.sched = v; }
+extern "C" void dpfs_gemm4_br(int v) { g_knobs.br = (v >= 0 && v <= 2) ? v : 0; }
+extern "C" void dpfs_gemm4_m32(int v) { g_knobs.m32 = v ? 1 : 0; }
+extern "C" void dpfs_gemm4_m32k(int v) { g_knobs.m32k = v & 3; }
+extern "C" void dpfs_gemm4_swb_depth(int d) { g_knobs.swb_depth = d == 1 ? 1 : 2; }
+extern "C" void dpfs_gemm4_sk_starve(int on) { g_knobs.sk_starve = on; }
+
+// gemm4_k's arguments in its parameter order (group_m comes from the knobs); the forms' own
+// arguments default to "none".
+struct KArgs {
+  const bf16* A;
+  const bf16* B;
+  void* C;
+  const float* bias;
+  int M, N, K, lda, ldb, ldc, kps, splits;
+  long long slab_stride;
+  unsigned a_bytes, b_bytes, c_bytes;
+  Rope rope;
+  Dual dual;
+  int dbg;
+  unsigned long long* diag;
+  SwiOut swo{};
+  SwiBwd swb{};
+  TnGroup grp{};
+  SkArgs sk{};
+};
+constexpr Rope kNoRope = {nullptr, nullptr, 0, 64};
+constexpr int kNoSwitch = 0x7fffffff;   // Dual::k_switch: no second buffer
+
+// The one place that maps a variant to gemm4_k's positional template list, and launches it.
+template <class V>
+static void launch(int grid, hipStream_t s, const KArgs& a) {
+  gemm4_k<V::AK, V::BKM, V::OUT, V::DIAG, V::FAST, V::SCHED, V::BN, V::ROPE, V::SWIGLU, V::SWB, V::BR, V::SA, V::M32,
+          V::GRP, V::SK><<<grid, 256, 0, s>>>(a.A, a.B, a.C, a.bias, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.kps, a.splits,
+                                              a.slab_stride, a.a_bytes, a.b_bytes, a.c_bytes, a.rope, g_knobs.group_m,
+                                              a.dual, a.dbg, a.diag, a.swo, a.swb, a.grp, a.sk);
+}
 
 // gate|up projection with SwiGLU in the epilogue (SwiOut): C[M, N] = A perm(B)^T + perm(bias)
 // (B / bias in the natural [gate | up] layout, read interleaved: reference.gu_perm),
@@ -1409,12 +1501,10 @@ extern "C" bool dpfs_gemm4_nt_swiglu(const void* A, const void* B, void* C, cons
   const long long items = (long long)((M + 255) / 256) * ((N + 255) / 256);
   if (items <= 0 || items >= (1ll << 31)) return false;
   const int grid = (int)std::min<long long>(items, g4_cu_count());
-  const Rope rope = {nullptr, nullptr, 0, 64};
-  const Dual dual = {nullptr, nullptr, 0x7fffffff, lda, ldb, 0u, 0u};
-  const SwiOut swo = {(bf16*)H, ldh, (unsigned)hspan};
-  gemm4_k<true, true, 0, 0, true, 1, 256, 0, true><<<grid, 256, 0, s>>>(
-      (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, K, 1, 0, a_bytes, b_bytes, (unsigned)cspan, rope,
-      g_g4_group_m, dual, 0, nullptr, swo);
+  KArgs a = {(const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, K, 1, 0, a_bytes, b_bytes, (unsigned)cspan,
+             kNoRope, {nullptr, nullptr, kNoSwitch, lda, ldb, 0u, 0u}, 0, nullptr};
+  a.swo = {(bf16*)H, ldh, (unsigned)hspan};
+  launch<SwigluFwd>(grid, s, a);
   return true;
 }
 
@@ -1422,10 +1512,6 @@ extern "C" bool dpfs_gemm4_nt_swiglu(const void* A, const void* B, void* C, cons
 // [M, K] (K-major), B = W_down [K, F] (F contiguous), gu [M, 2F] (interleaved if perm), dgu
 // [M, 2F] natural, part [2 * ceil(M / 256), 2F] fp32 (every row written).  Returns false
 // (nothing launched) where the 256-wide FAST kernel does not apply.
-// gate / up row blocks in flight in the SWB epilogue (1 or 2; A/B hook, tools/ab_attr.py)
-static int g_g4_swb_depth = 2;
-extern "C" void dpfs_gemm4_swb_depth(int d) { g_g4_swb_depth = d == 1 ? 1 : 2; }
-
 extern "C" bool dpfs_gemm4_nn_swiglu_bwd(const void* A, const void* B, const void* gu, void* dgu, float* part, int M,
                                          int F, int K, int lda, int ldb, int ldgu, int lddgu, int perm,
                                          unsigned a_bytes, unsigned b_bytes, hipStream_t s) {
@@ -1439,19 +1525,13 @@ extern "C" bool dpfs_gemm4_nn_swiglu_bwd(const void* A, const void* B, const voi
   const long long items = tiles_m * ((F + 255) / 256);
   if (items <= 0 || items >= (1ll << 31)) return false;
   const int grid = (int)std::min<long long>(items, g4_cu_count());
-  const Rope rope = {nullptr, nullptr, 0, 64};
-  const Dual dual = {nullptr, nullptr, 0x7fffffff, lda, ldb, 0u, 0u};
+  KArgs a = {(const bf16*)A, (const bf16*)B, nullptr, nullptr, M, F, K, lda, ldb, F, K, 1, 0, a_bytes, b_bytes, 0u,
+             kNoRope, {nullptr, nullptr, kNoSwitch, lda, ldb, 0u, 0u}, 0, nullptr};
   // no partials buffer (no bias gradient): a zero-record descriptor drops every partial store
-  const SwiBwd swb = {(const bf16*)gu, (bf16*)dgu, part, ldgu, lddgu, perm ? 1 : 0, (unsigned)guspan, (unsigned)dspan,
-                      part ? (unsigned)pspan : 0u};
-  if (g_g4_swb_depth == 1)
-    gemm4_k<true, false, 0, 0, true, 1, 256, 0, false, 1><<<grid, 256, 0, s>>>(
-        (const bf16*)A, (const bf16*)B, nullptr, nullptr, M, F, K, lda, ldb, F, K, 1, 0, a_bytes, b_bytes, 0u, rope,
-        g_g4_group_m, dual, 0, nullptr, SwiOut{}, swb);
-  else
-    gemm4_k<true, false, 0, 0, true, 1, 256, 0, false, 2><<<grid, 256, 0, s>>>(
-        (const bf16*)A, (const bf16*)B, nullptr, nullptr, M, F, K, lda, ldb, F, K, 1, 0, a_bytes, b_bytes, 0u, rope,
-        g_g4_group_m, dual, 0, nullptr, SwiOut{}, swb);
+  a.swb = {(const bf16*)gu, (bf16*)dgu, part, ldgu, lddgu, perm ? 1 : 0, (unsigned)guspan, (unsigned)dspan,
+           part ? (unsigned)pspan : 0u};
+  if (g_knobs.swb_depth == 1) launch<SwigluBwd<1>>(grid, s, a);
+  else launch<SwigluBwd<2>>(grid, s, a);
   return true;
 }
 
@@ -1465,12 +1545,6 @@ extern "C" long long dpfs_gemm4_sk_ws(int M, int N, int K) {
   if (tiles * 2 != 3LL * cus) return -1;
   const long long E = cus / 2;
   return E * 4 * 16384 + E * 4 + 4;
-}
-static float* g_g4_sk_ws = nullptr;
-static long long g_g4_sk_ws_floats = 0;
-extern "C" void dpfs_gemm4_set_sk_ws(float* p, long long n) {
-  g_g4_sk_ws = p;
-  g_g4_sk_ws_floats = n;
 }
 // Sticky error word of the stream-K hand-off: host-mapped (the host reads it without a device
 // sync) and never cleared by a launch, so a consumer whose bounded wait for its producer's
@@ -1501,31 +1575,79 @@ extern "C" int dpfs_gemm4_sk_error(int reset) {
   if (reset) __atomic_store_n(g_g4_sk_err_host, 0u, __ATOMIC_RELAXED);
   return v;
 }
-// Test hook: the next stream-K launch runs its consumers with their producers' flags never
-// set (the producers skip the flag store), so every consumer's wait times out.
-static int g_g4_sk_starve = 0;
-extern "C" void dpfs_gemm4_sk_starve(int on) { g_g4_sk_starve = on; }
+
+// What the choice of a variant depends on besides (layout, output) and the knobs.
+struct Shape {
+  bool fast;   // every item's K range a multiple of 64 (Variant::FAST applies)
+  bool prod;   // fast, and one DMA piece per MFMA row (Variant::SCHED 1)
+  int bn;      // tile width, 256 or 192 (192: bf16 non-split, no RoPE only)
+  bool stream_stores;
+  int rope_cols, rope_hd;
+};
+
+// V at the shape's tile width (fp32 outputs are always 256 wide).
+template <class V>
+static void launch_width(const Shape& sh, int grid, hipStream_t s, const KArgs& a) {
+  if constexpr (V::OUT == 0) {
+    if (sh.bn == 192) return launch<Wide192<V>>(grid, s, a);
+  }
+  launch<V>(grid, s, a);
+}
+
+// The production choice for layout L (NT / NN / TN) and output OUT.
+template <class L, int OUT>
+static void launch_plain(const Shape& sh, int grid, hipStream_t s, const KArgs& a) {
+  constexpr bool nt = L::AK && L::BKM, tn = !L::AK && !L::BKM;
+  const G4Knobs& kn = g_knobs;
+  if constexpr (nt && OUT == 0) {
+    if (sh.rope_cols > 0) {
+      if (sh.fast && sh.rope_hd == 64) return launch<Roped<Fast<L, OUT>, 64>>(grid, s, a);
+      if (sh.fast) return launch<Roped<Fast<L, OUT>, 128>>(grid, s, a);
+      if (sh.rope_hd == 64) return launch<Roped<Checked<L, OUT>, 64>>(grid, s, a);
+      return launch<Roped<Checked<L, OUT>, 128>>(grid, s, a);
+    }
+  }
+  if constexpr (tn && OUT == 1) {
+    if (sh.prod && kn.m32) {
+      if (kn.br_tn == 1) return launch<Mfma32<Fast<L, OUT, 1>>>(grid, s, a);
+      if (kn.br_tn == 2) return launch<Mfma32<Fast<L, OUT, 2>>>(grid, s, a);
+      return launch<Mfma32<Fast<L, OUT>>>(grid, s, a);
+    }
+  }
+  if constexpr (L::AK && OUT == 1) {
+    if (sh.prod && (kn.m32k & 1)) return launch<Mfma32<Fast<L, OUT>>>(grid, s, a);
+  }
+  if constexpr (L::AK && OUT == 0) {
+    if (sh.prod && (kn.m32k & 2) && sh.bn == 256 && sh.rope_cols == 0) {
+      if (sh.stream_stores) return launch<StreamStores<Mfma32<Fast<L, OUT>>>>(grid, s, a);
+      return launch<Mfma32<Fast<L, OUT>>>(grid, s, a);
+    }
+  }
+  if constexpr (OUT == 0) {   // (no non-temporal form of the fp32 stores)
+    if (sh.prod && sh.stream_stores && sh.rope_cols == 0) return launch_width<StreamStores<Fast<L, OUT>>>(sh, grid, s, a);
+  }
+  if (sh.prod) {
+    if (kn.br == 1) return launch_width<Fast<L, OUT, 1>>(sh, grid, s, a);
+    if (kn.br == 2) return launch_width<Fast<L, OUT, 2>>(sh, grid, s, a);
+    return launch_width<Fast<L, OUT>>(sh, grid, s, a);
+  }
+  if (sh.fast) return launch_width<FastPaired<L, OUT>>(sh, grid, s, a);
+  launch_width<Checked<L, OUT>>(sh, grid, s, a);
+}
 
 // Launch v4.  layout: 0 = NT (A K-major, B K-major), 1 = NN (B MN-major), 2 = TN (both
 // MN-major, fp32 out).  Returns false (nothing launched) when a span does not fit the 32-bit
 // buffer descriptors or a contiguous dimension is not a multiple of 8.
-extern "C" bool dpfs_gemm4_launch(int layout, int out_f32, const void* A, const void* B, void* C, const float* bias,
-                                  int M, int N, int K, int lda, int ldb, int ldc, int kps, int splits,
-                                  long long slab_stride, unsigned a_bytes, unsigned b_bytes, const int64_t* rope_pos,
-                                  const float* rope_tab, int rope_cols, int rope_hd, const void* A2, const void* B2,
-                                  int k_switch, int lda2, int ldb2, unsigned a2_bytes, unsigned b2_bytes,
-                                  int bn_force, hipStream_t s) {
-  // bn_force: tile width of a non-split bf16 GEMM, 0 = chosen per shape, 256 / 192 forced;
-  // | 0x100: the bf16 output written with non-temporal stores (plain NT / NN); | 0x200: the
-  // stream-K kernel where it applies (dpfs_gemm4_sk_ws, workspace set by dpfs_gemm4_set_sk_ws)
-  const bool ntst = (bn_force & 0x100) != 0;
-  const bool skreq = (bn_force & 0x200) != 0;
-  bn_force &= 0xff;
+extern "C" bool dpfs_gemm4_launch(const dpfs_gemm4_args* args, hipStream_t s) {
+  const dpfs_gemm4_args& g = *args;
+  const G4Knobs& kn = g_knobs;
+  const int layout = g.layout, M = g.M, N = g.N, K = g.K, splits = g.splits, rope_cols = g.rope_cols;
+  const bool out_f32 = g.out_f32 != 0;
   if (M <= 0 || N <= 0 || (N % 8) || (K % 8)) return false;
   if (layout == 2 && (M % 8)) return false;
-  if (rope_cols > 0 && rope_hd != 64 && rope_hd != 128) return false;
-  if (kps % 32) return false;
-  const long long cspan = ((long long)(M - 1) * ldc + N) * (out_f32 ? 4 : 2);
+  if (rope_cols > 0 && g.rope_hd != 64 && g.rope_hd != 128) return false;
+  if (g.kps % 32) return false;
+  const long long cspan = ((long long)(M - 1) * g.ldc + N) * (out_f32 ? 4 : 2);
   if (cspan >= (1ll << 32) - 16) return false;
   // 256 x 192 tiles where whole waves of tiles over the CUs come out shorter: 384 tiles of
   // 256 x 256 (N = 768 at 32k rows) are 1.5 per CU, i.e. two rounds on half the chip; 512
@@ -1534,9 +1656,9 @@ extern "C" bool dpfs_gemm4_launch(int layout, int out_f32, const void* A, const 
   const int cus = g4_cu_count();
   int bn = 256;
   if (!out_f32 && splits == 1 && rope_cols == 0) {
-    if (bn_force == 192) {
+    if (g.width == 192) {
       bn = 192;
-    } else if (bn_force == 0) {
+    } else if (g.width == 0) {
       const long long tm = (M + 255) / 256;
       const long long r256 = (tm * ((N + 255) / 256) + cus - 1) / cus;
       const long long r192 = (tm * ((N + 191) / 192) + cus - 1) / cus;
@@ -1546,180 +1668,89 @@ extern "C" bool dpfs_gemm4_launch(int layout, int out_f32, const void* A, const 
   const long long items = (long long)((M + 255) / 256) * ((N + bn - 1) / bn) * splits;
   if (items <= 0 || items >= (1ll << 31)) return false;
   const int grid = (int)std::min<long long>(items, cus);
-  const Rope rope = {rope_pos, rope_tab, rope_cols, rope_hd};
-  const Dual dual = {(const bf16*)A2, (const bf16*)B2, A2 ? k_switch : 0x7fffffff, lda2, ldb2, a2_bytes, b2_bytes};
-  const unsigned cb = (g_g4_ablate & 1) ? 0u : (unsigned)cspan;
-  if (g_g4_ablate & 2) {
-    a_bytes = b_bytes = a2_bytes = b2_bytes = 0u;
-  }
   // FAST (descriptor-advancing DMA stream): every item's K range a multiple of 64
   // (not under the zero-operand ablation: FAST's per-item record counts are the bytes past the
   // item's K offset, which a zero-record descriptor would underflow)
-  const bool fast = g_g4_sched != 2 && !(g_g4_ablate & 2) && K % 64 == 0 && kps % 64 == 0 &&
-                    (!A2 || k_switch % 64 == 0);
-  const int sched = g_g4_sched == 1 ? 0 : 1;
-#define G4_ARGS                                                                                            \
-  (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes, cb, \
-      rope, g_g4_group_m, dual, g_g4_ablate & ~3, nullptr
-#define G4_LAUNCH(AK_, BK_, OUT_)                                                                    \
-  do {                                                                                            \
-    if constexpr (AK_ && BK_ && OUT_ == 0) {                                                      \
-      if (rope_cols > 0) {                                                                        \
-        if (fast && rope_hd == 64)                                                                \
-          gemm4_k<AK_, BK_, OUT_, 0, true, 1, 256, 64><<<grid, 256, 0, s>>>(G4_ARGS);        \
-        else if (fast)                                                                            \
-          gemm4_k<AK_, BK_, OUT_, 0, true, 1, 256, 128><<<grid, 256, 0, s>>>(G4_ARGS);       \
-        else if (rope_hd == 64)                                                                   \
-          gemm4_k<AK_, BK_, OUT_, 0, false, 0, 256, 64><<<grid, 256, 0, s>>>(G4_ARGS);       \
-        else                                                                                      \
-          gemm4_k<AK_, BK_, OUT_, 0, false, 0, 256, 128><<<grid, 256, 0, s>>>(G4_ARGS);      \
-        break;                                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if constexpr (!AK_ && !BK_ && OUT_ == 1) {                                                    \
-      if (fast && sched == 1 && g_g4_m32) {                                                       \
-        if (g_g4_br_tn == 1)                                                                      \
-          gemm4_k<false, false, 1, 0, true, 1, 256, 0, false, false, 1, 0, true>                  \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        else if (g_g4_br_tn == 2)                                                                 \
-          gemm4_k<false, false, 1, 0, true, 1, 256, 0, false, false, 2, 0, true>                  \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        else                                                                                      \
-          gemm4_k<false, false, 1, 0, true, 1, 256, 0, false, false, 0, 0, true>                  \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        break;                                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if constexpr (AK_ && OUT_ == 1) {                                                             \
-      if (fast && sched == 1 && (g_g4_m32k & 1)) {                                                \
-        gemm4_k<AK_, BK_, 1, 0, true, 1, 256, 0, false, false, 0, 0, true>                        \
-            <<<grid, 256, 0, s>>>(G4_ARGS);                                                       \
-        break;                                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if constexpr (AK_ && OUT_ == 0) {                                                             \
-      if (fast && sched == 1 && (g_g4_m32k & 2) && bn == 256 && rope_cols == 0) {                 \
-        if (ntst)                                                                                 \
-          gemm4_k<AK_, BK_, 0, 0, true, 1, 256, 0, false, false, 0, 2, true>                      \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        else                                                                                      \
-          gemm4_k<AK_, BK_, 0, 0, true, 1, 256, 0, false, false, 0, 0, true>                      \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        break;                                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if (fast && sched == 1 && OUT_ == 0 && ntst && rope_cols == 0) {                             \
-      if (bn == 192)                                                                              \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 1, 192, 0, false, false, 0, 2><<<grid, 256, 0, s>>>(G4_ARGS); \
-      else                                                                                        \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 1, 256, 0, false, false, 0, 2><<<grid, 256, 0, s>>>(G4_ARGS); \
-    } else if (fast && sched == 1) {                                                              \
-      if (OUT_ == 0 && bn == 192) {                                                               \
-        if (g_g4_br == 1)                                                                         \
-          gemm4_k<AK_, BK_, OUT_, 0, true, 1, (OUT_ == 0 ? 192 : 256), 0, false, false, 1>         \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        else if (g_g4_br == 2)                                                                    \
-          gemm4_k<AK_, BK_, OUT_, 0, true, 1, (OUT_ == 0 ? 192 : 256), 0, false, false, 2>         \
-              <<<grid, 256, 0, s>>>(G4_ARGS);                                                     \
-        else                                                                                      \
-          gemm4_k<AK_, BK_, OUT_, 0, true, 1, (OUT_ == 0 ? 192 : 256)><<<grid, 256, 0, s>>>(G4_ARGS); \
-      } else if (g_g4_br == 1) {                                                                  \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 1, 256, 0, false, false, 1><<<grid, 256, 0, s>>>(G4_ARGS); \
-      } else if (g_g4_br == 2) {                                                                  \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 1, 256, 0, false, false, 2><<<grid, 256, 0, s>>>(G4_ARGS); \
-      } else {                                                                                    \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 1><<<grid, 256, 0, s>>>(G4_ARGS);                   \
-      }                                                                                           \
-    } else if (fast) {                                                                            \
-      if (OUT_ == 0 && bn == 192)                                                                 \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 0, (OUT_ == 0 ? 192 : 256)><<<grid, 256, 0, s>>>(G4_ARGS); \
-      else                                                                                        \
-        gemm4_k<AK_, BK_, OUT_, 0, true, 0><<<grid, 256, 0, s>>>(G4_ARGS);                   \
-    } else if (OUT_ == 0 && bn == 192) {                                                          \
-      gemm4_k<AK_, BK_, OUT_, 0, false, 0, (OUT_ == 0 ? 192 : 256)><<<grid, 256, 0, s>>>(G4_ARGS); \
-    } else {                                                                                      \
-      gemm4_k<AK_, BK_, OUT_><<<grid, 256, 0, s>>>(G4_ARGS);                                 \
-    }                                                                                             \
-  } while (0)
-  if (skreq && layout != 2 && !out_f32 && splits == 1 && rope_cols == 0 && fast && sched == 1 && !A2 && !g_g4_ablate) {
+  const bool fast = kn.sched != 2 && !(kn.ablate & 2) && K % 64 == 0 && g.kps % 64 == 0 &&
+                    (!g.A2 || g.k_switch % 64 == 0);
+  const Shape sh = {fast, fast && kn.sched != 1, bn, g.stream_stores != 0, rope_cols, g.rope_hd};
+  KArgs a = {(const bf16*)g.A, (const bf16*)g.B, g.C, g.bias, M, N, K, g.lda, g.ldb, g.ldc, g.kps, splits,
+             g.slab_stride, g.a_bytes, g.b_bytes, (unsigned)cspan,
+             {g.rope_pos, g.rope_tab, rope_cols, rope_cols > 0 ? g.rope_hd : 64},
+             {(const bf16*)g.A2, (const bf16*)g.B2, g.A2 ? g.k_switch : kNoSwitch, g.lda2, g.ldb2, g.a2_bytes, g.b2_bytes},
+             kn.ablate & ~3, nullptr};
+  if (kn.ablate & 1) a.c_bytes = 0u;
+  if (kn.ablate & 2) a.a_bytes = a.b_bytes = 0u;
+
+  const bool nt_bf16_256 = layout == 0 && !out_f32 && bn == 256;
+  if (g.stream_k && layout != 2 && !out_f32 && splits == 1 && rope_cols == 0 && sh.prod && !g.A2 && !kn.ablate) {
     const long long need = dpfs_gemm4_sk_ws(M, N, K);
-    if (need > 0 && g_g4_sk_ws && g_g4_sk_ws_floats >= need) {
+    if (need > 0 && g.sk_ws && g.sk_ws_floats >= need) {
       const int E = cus / 2;
-      SkArgs sk;
-      sk.part = g_g4_sk_ws;
-      sk.flags = reinterpret_cast<unsigned*>(g_g4_sk_ws + (long long)E * 4 * 16384);
-      sk.err = sk_err_word();
-      if (!sk.err) return false;
-      sk.extra = E;
-      sk.starve = g_g4_sk_starve;
-      g_g4_sk_starve = 0;
-      if (hipMemsetAsync(sk.flags, 0, (size_t)(E * 4 + 1) * 4, s) != hipSuccess) return false;
-#define G4_SK(AK_, BK_, SA_)                                                                                  \
-  gemm4_k<AK_, BK_, 0, 0, true, 1, 256, 0, false, 0, 0, SA_, false, false, true><<<cus, 256, 0, s>>>(       \
-      (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, K, 1, 0, a_bytes, b_bytes, cb, rope, \
-      g_g4_group_m, dual, 0, nullptr, SwiOut{}, SwiBwd{}, TnGroup{}, sk)
+      a.kps = K;
+      a.slab_stride = 0;
+      a.sk.part = g.sk_ws;
+      a.sk.flags = reinterpret_cast<unsigned*>(g.sk_ws + (long long)E * 4 * 16384);
+      a.sk.err = sk_err_word();
+      if (!a.sk.err) return false;
+      a.sk.extra = E;
+      a.sk.starve = g_knobs.sk_starve;
+      g_knobs.sk_starve = 0;
+      if (hipMemsetAsync(a.sk.flags, 0, (size_t)(E * 4 + 1) * 4, s) != hipSuccess) return false;
       if (layout == 0) {
-        if (ntst) G4_SK(true, true, 2);
-        else G4_SK(true, true, 0);
+        if (sh.stream_stores) launch<StreamK<StreamStores<Fast<NT, 0>>>>(cus, s, a);
+        else launch<StreamK<Fast<NT, 0>>>(cus, s, a);
       } else {
-        if (ntst) G4_SK(true, false, 2);
-        else G4_SK(true, false, 0);
+        if (sh.stream_stores) launch<StreamK<StreamStores<Fast<NN, 0>>>>(cus, s, a);
+        else launch<StreamK<Fast<NN, 0>>>(cus, s, a);
       }
-#undef G4_SK
       return true;
     }
   }
-  if ((g_g4_ablate & 32) && g_g4_diag && layout == 0 && !out_f32 && bn == 256) {
-    gemm4_k<true, true, 0, 2, true, 1><<<grid, 256, 0, s>>>((const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda,
-                                                            ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes, cb,
-                                                            rope, g_g4_group_m, dual, g_g4_ablate & ~51, g_g4_diag);
+  if ((kn.ablate & 32) && kn.diag && nt_bf16_256) {
+    // NT: the DIAG build with no DMA issued
+    a.dbg = kn.ablate & ~51;
+    a.diag = kn.diag;
+    launch<Diag<Fast<NT, 0>, 2>>(grid, s, a);
     return true;
   }
-  if ((g_g4_ablate & (4 | 8 | 1024)) && layout == 0 && !out_f32 && bn == 256 && fast && rope_cols == 0) {
+  if ((kn.ablate & (4 | 8 | 1024)) && nt_bf16_256 && fast && rope_cols == 0) {
     // the ablation build (1024: the same build with no ablation, the cost of its branches)
-    gemm4_k<true, true, 0, 3, true, 1><<<grid, 256, 0, s>>>((const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda,
-                                                            ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes, cb,
-                                                            rope, g_g4_group_m, dual, g_g4_ablate, nullptr);
+    a.dbg = kn.ablate;
+    launch<Diag<Fast<NT, 0>, 3>>(grid, s, a);
     return true;
   }
-  if ((g_g4_ablate & 128) && layout == 0 && !out_f32 && bn == 256 && fast && rope_cols == 0) {
+  if ((kn.ablate & 128) && nt_bf16_256 && fast && rope_cols == 0) {
     // A/B: the bf16 epilogue stores with the non-temporal hint (streaming output, aux nt)
-    gemm4_k<true, true, 0, 0, true, 1, 256, 0, false, false, 0, 2><<<grid, 256, 0, s>>>(
-        (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes, cb,
-        rope, g_g4_group_m, dual, 0, nullptr);
+    a.dbg = 0;
+    launch<StreamStores<Fast<NT, 0>>>(grid, s, a);
     return true;
   }
-  if ((g_g4_ablate & (16 | 32)) && g_g4_diag && layout == 2 && fast && g_g4_m32) {
+  if ((kn.ablate & (16 | 32)) && kn.diag && layout == 2 && fast && kn.m32) {
     // TN 32x32x16: the DIAG builds (16: per-wave cycle split; 32: the same with no DMA issued)
-    const Rope rp = rope;
-    if (g_g4_ablate & 32)
-      gemm4_k<false, false, 1, 2, true, 1, 256, 0, false, false, 0, 0, true><<<grid, 256, 0, s>>>(
-          (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes,
-          cb, rp, g_g4_group_m, dual, 0, g_g4_diag);
-    else
-      gemm4_k<false, false, 1, 1, true, 1, 256, 0, false, false, 0, 0, true><<<grid, 256, 0, s>>>(
-          (const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda, ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes,
-          cb, rp, g_g4_group_m, dual, 0, g_g4_diag);
+    a.dbg = 0;
+    a.diag = kn.diag;
+    if (kn.ablate & 32) launch<Diag<Mfma32<Fast<TN, 1>>, 2>>(grid, s, a);
+    else launch<Diag<Mfma32<Fast<TN, 1>>, 1>>(grid, s, a);
     return true;
   }
-  if ((g_g4_ablate & 16) && g_g4_diag && layout == 0 && !out_f32 && bn == 256 && fast) {
-    gemm4_k<true, true, 0, 1, true, 1><<<grid, 256, 0, s>>>((const bf16*)A, (const bf16*)B, C, bias, M, N, K, lda,
-                                                            ldb, ldc, kps, splits, slab_stride, a_bytes, b_bytes, cb,
-                                                            rope, g_g4_group_m, dual, g_g4_ablate & ~19, g_g4_diag);
+  if ((kn.ablate & 16) && kn.diag && nt_bf16_256 && fast) {
+    // NT: the DIAG build with the per-wave cycle split
+    a.dbg = kn.ablate & ~19;
+    a.diag = kn.diag;
+    launch<Diag<Fast<NT, 0>, 1>>(grid, s, a);
     return true;
   }
   if (layout == 0) {
-    if (out_f32) G4_LAUNCH(true, true, 1);
-    else G4_LAUNCH(true, true, 0);
+    if (out_f32) launch_plain<NT, 1>(sh, grid, s, a);
+    else launch_plain<NT, 0>(sh, grid, s, a);
   } else if (layout == 1) {
-    if (out_f32) G4_LAUNCH(true, false, 1);
-    else G4_LAUNCH(true, false, 0);
+    if (out_f32) launch_plain<NN, 1>(sh, grid, s, a);
+    else launch_plain<NN, 0>(sh, grid, s, a);
   } else {
     if (!out_f32) return false;
-    G4_LAUNCH(false, false, 1);
+    launch_plain<TN, 1>(sh, grid, s, a);
   }
-#undef G4_ARGS
-#undef G4_LAUNCH
   return true;
 }
 
@@ -1803,7 +1834,7 @@ static bool tn_group_plan(int n, const int* M, const int* N, int K0, int K1, int
 // K1 > 0: the rows continue in second buffers (lda2 / ldb2) for K1 more rows.
 extern "C" long long dpfs_gemm_tn_group_ws(int n, const int* M, const int* N, const int* lda, const int* ldb, int K,
                                            const int* acc, const int* lda2, const int* ldb2, int K1) {
-  if (n < 1 || n > 4 || K % 64 || !g_g4_m32 || K <= 0 || K1 < 0 || (K1 && (K1 % 64 || !lda2 || !ldb2))) return -1;
+  if (n < 1 || n > 4 || K % 64 || !g_knobs.m32 || K <= 0 || K1 < 0 || (K1 && (K1 % 64 || !lda2 || !ldb2))) return -1;
   bool any_acc = false;
   for (int g = 0; g < n; ++g) {
     if (M[g] <= 0 || N[g] <= 0 || M[g] % 8 || N[g] % 8 || lda[g] < M[g] || ldb[g] < N[g]) return -1;
@@ -1878,17 +1909,13 @@ extern "C" int dpfs_gemm_tn_group(int n, const void* const* A, const void* const
   if (items >= (1ll << 31)) return 0;
   grp.total = (int)items;
   const int grid = (int)std::min<long long>(items, g4_cu_count());
-  const Rope rope = {nullptr, nullptr, 0, 64};
-  const Dual dual = {nullptr, nullptr, 0x7fffffff, 0, 0, 0u, 0u};
-#define G4_GRP(BR_)                                                                                         \
-  gemm4_k<false, false, 1, 0, true, 1, 256, 0, false, false, BR_, 0, true, true><<<grid, 256, 0, s>>>(       \
-      grp.d[0].A, grp.d[0].B, grp.d[0].C, nullptr, 256, 256, K1 ? ksw + K1 : K, lda[0], ldb[0], N[0], kps, S, 0, \
-      grp.d[0].a_bytes, grp.d[0].b_bytes, grp.d[0].c_bytes, rope, g_g4_group_m, dual, 0, nullptr, SwiOut{},     \
-      SwiBwd{}, grp)
-  if (g_g4_br_tn == 1) G4_GRP(1);
-  else if (g_g4_br_tn == 2) G4_GRP(2);
-  else G4_GRP(0);
-#undef G4_GRP
+  const TnGemm& g0 = grp.d[0];
+  KArgs a = {g0.A, g0.B, g0.C, nullptr, 256, 256, K1 ? ksw + K1 : K, lda[0], ldb[0], N[0], kps, S, 0, g0.a_bytes,
+             g0.b_bytes, g0.c_bytes, kNoRope, {nullptr, nullptr, kNoSwitch, 0, 0, 0u, 0u}, 0, nullptr};
+  a.grp = grp;
+  if (g_knobs.br_tn == 1) launch<TnGrouped<1>>(grid, s, a);
+  else if (g_knobs.br_tn == 2) launch<TnGrouped<2>>(grid, s, a);
+  else launch<TnGrouped<0>>(grid, s, a);
   if (slabs) {
     long long gr = (mn / 4 + 255) / 256;
     if (gr > 4096) gr = 4096;

@@ -1034,6 +1034,39 @@ def test_gemm_v4_bitwise_equals_v3(C, M, N, K, sched, bn):
     assert torch.equal(nn4, nn3)
 
 
+def test_gemm_v4_variants_and_barrier_rows_bitwise(C):
+    """Every per-call v4 variant (tile width per shape or forced, plain or non-temporal stores;
+    0 1 2 4 5 6) at every gemm4_br (rows of MFMAs ahead of the step's barrier) gives
+    the v3 kernel's bits for NT (+ bias) and NN, on the descriptor-advancing DMA stream (K =
+    128) and the per-lane-checked one (K = 96), on ragged M / N; the TN 32x32x16 loop gives the
+    same bits at every gemm4_br_tn.  The variants differ only in speed, so a launcher that picks
+    the wrong one is invisible to the numeric tests: this at least runs each of them."""
+    torch.manual_seed(41)
+    try:
+        for M, N, K in [(257, 264, 128), (257, 264, 96)]:
+            a = torch.randn(M, K, device=DEV).bfloat16()
+            bt = torch.randn(N, K, device=DEV).bfloat16()
+            b_nn = torch.randn(K, N, device=DEV).bfloat16()
+            bias = torch.randn(N, device=DEV)
+            nt3, nn3 = C.gemm_nt(a, bt, bias, variant=3), C.gemm_nn(a, b_nn, variant=3)
+            for br in (0, 1, 2):
+                C.gemm4_br(br)
+                for v in (0, 1, 2, 4, 5, 6):
+                    assert torch.equal(C.gemm_nt(a, bt, bias, variant=v), nt3), f"NT K={K} br={br} variant={v}"
+                    assert torch.equal(C.gemm_nn(a, b_nn, variant=v), nn3), f"NN K={K} br={br} variant={v}"
+        M, N, K = 264, 520, 256
+        a = torch.randn(K, M, device=DEV).bfloat16()
+        b = torch.randn(K, N, device=DEV).bfloat16()
+        C.gemm4_br_tn(0)
+        tn0 = C.gemm_tn(a, b)
+        for br in (1, 2):
+            C.gemm4_br_tn(br)
+            assert torch.equal(C.gemm_tn(a, b), tn0), f"TN gemm4_br_tn={br}"
+    finally:
+        C.gemm4_br(2)
+        C.gemm4_br_tn(0)
+
+
 @pytest.mark.parametrize("M,N,K", [(256, 256, 256), (2304, 768, 4096), (96, 768, 1000), (776, 2104, 8192)])
 @pytest.mark.parametrize("splits", [0, 3])
 def test_gemm_v4_tn(C, M, N, K, splits):
