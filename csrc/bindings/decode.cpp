@@ -59,6 +59,64 @@ void kv_append(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc, torch::Ten
                                                 stream());
 }
 
+// The real new tokens of every sequence of a chunk: B device int32, or none (T for every row).
+const int* check_chunk_n(const c10::optional<torch::Tensor>& n, int64_t B, const torch::Tensor& like) {
+  if (!n.has_value()) return nullptr;
+  check_cuda(*n, "n");
+  TORCH_CHECK(n->scalar_type() == torch::kInt32 && n->is_contiguous() && n->numel() == B && n->device() == like.device(),
+              "n must be a contiguous device int32 tensor of B = ", B, " elements");
+  return n->data_ptr<int>();
+}
+
+// o[B*T, H*hd]: query (b, t) (row b*T + t of q, the q part of the packed qkv rows) attends keys
+// [0, len[b] + t] of the cache, which already holds the chunk's rows (_kv_append_chunk).  A
+// query with t >= n[b] or len[b] + t >= T_max gives zeros.  Bound with a leading underscore:
+// the module's recorded public surface (tests/golden/ext_api.txt) is left as it is.
+torch::Tensor attn_extend(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor len,
+                          c10::optional<torch::Tensor> n, double scale) {
+  check_rowmajor(q, "q");
+  check_cache(kc, "k_cache");
+  check_cache(vc, "v_cache");
+  TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
+  const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  const bool rows = check_len(len, B);
+  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, "attn_extend: head_dim 32, 64 or 128");
+  TORCH_CHECK(q.size(0) % B == 0 && q.size(0) >= B && q.size(1) >= H * hd && q.stride(0) % 8 == 0 &&
+                  q.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_extend: q must be bf16 rows [B*T, >= H*hd], row stride % 8 == 0, 16-byte aligned");
+  const int64_t T = q.size(0) / B;
+  TORCH_CHECK(B * H <= 65535 && B * T * H * hd < (1LL << 31) && Tmax < (1LL << 30), "attn_extend: shape too large");
+  const int* np = check_chunk_n(n, B, q);
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({B * T, H * hd}, q.options());
+  dpfs_attn_extend(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(), rows ? 1 : 0, np,
+                   o.data_ptr(), (int)B, (int)T, (int)H, (int)hd, (int)Tmax, (float)scale, stream());
+  return o;
+}
+
+// The k / v parts of packed qkv row b*T + t ([B*T, 3*H*hd]) go to cache row len[b] + t, for
+// t < n[b] (n none: T) and len[b] + t < T_max; nothing else is written.
+void kv_append_chunk(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc, torch::Tensor len,
+                     c10::optional<torch::Tensor> n) {
+  check_rowmajor(qkv, "qkv");
+  check_cache(kc, "k_cache");
+  check_cache(vc, "v_cache");
+  TORCH_CHECK(kc.sizes() == vc.sizes(), "k / v cache shapes differ");
+  const int64_t B = kc.size(0), Tmax = kc.size(1), H = kc.size(2), hd = kc.size(3);
+  const bool rows = check_len(len, B);
+  TORCH_CHECK(qkv.size(0) % B == 0 && qkv.size(0) >= B && qkv.size(1) == 3 * H * hd && qkv.stride(0) % 8 == 0 &&
+                  (H * hd) % 8 == 0 && qkv.scalar_type() == torch::kBFloat16 &&
+                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "kv_append_chunk: qkv must be [B*T, 3*H*hd] bf16, H*hd % 8 == 0, 16-byte aligned");
+  const int64_t T = qkv.size(0) / B;
+  TORCH_CHECK(B * T < (1LL << 31) && Tmax < (1LL << 30), "kv_append_chunk: shape too large");
+  const int* np = check_chunk_n(n, B, qkv);
+  const at::DeviceGuard g(qkv.device());
+  const char* p = static_cast<const char*>(qkv.data_ptr());
+  dpfs_kv_append_chunk(p + H * hd * 2, p + 2 * H * hd * 2, qkv.stride(0), kc.data_ptr(), vc.data_ptr(),
+                       len.data_ptr<int>(), rows ? 1 : 0, np, (int)B, (int)T, (int)H, (int)hd, (int)Tmax, stream());
+}
+
 // y[M, N] = x[M, K] w[N, K]^T (+ bias) for M <= 16 (decode-step projections); with swiglu,
 // x is the packed [M, 2K] gate|up output and the operand is silu(gate) * up.
 bool gemv_nt_ok(torch::Tensor x, torch::Tensor w, bool swiglu) {
@@ -198,6 +256,10 @@ void bind_decode(py::module_& m) {
   m.def("kv_append", &kv_append, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"));
   m.def("step_advance", &step_advance, py::arg("len"), py::arg("pos"));
   m.def("_step_advance_rows", &step_advance_rows, py::arg("len"), py::arg("pos"), py::arg("t_max"));
+  m.def("_attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"),
+        py::arg("n"), py::arg("scale"));
+  m.def("_kv_append_chunk", &kv_append_chunk, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"),
+        py::arg("n") = py::none());
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);

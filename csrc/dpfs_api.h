@@ -37,6 +37,12 @@ int dpfs_attn_bwd(const void* dout, const void* q, const void* k, const void* v,
                   hipStream_t s, float* dbias, float* bws, int impl_req);
 long long dpfs_attn_bias_ws(int B, int T, int H, int hd);
 
+// kernels/attn_extend.hip
+void dpfs_attn_extend(const void* q, long long ldq, const void* kc, const void* vc, const int* len, int len_rows,
+                      const int* n, void* o, int B, int T, int H, int HD, int Tmax, float scale, hipStream_t s);
+void dpfs_kv_append_chunk(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc, const int* len,
+                          int len_rows, const int* n, int B, int T, int H, int HD, int Tmax, hipStream_t s);
+
 // kernels/attention_fused.hip
 void dpfs_attn_bwd_dkdv4(int items, const void* q, const void* k, const void* v, const void* dout, const float* lsn,
                          const float* ndel, void* dk, void* dv, int T, int H, int BH, long long ldq, long long ldk,

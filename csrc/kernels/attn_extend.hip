@@ -1,0 +1,316 @@
+// Prefill against a KV cache (gfx950): T > 1 new tokens of every sequence attend the keys the
+// cache already holds plus the causal part of their own chunk.  This is the case between the
+// causal flash prefill (attention.hip: empty cache) and the single-query attn_decode
+// (decode.hip: one new token); generation.py uses it for chunked prompts and for multi-token
+// continuations of uniform and ragged caches.
+//
+//   kv_append_chunk_k  the k / v parts of packed qkv row (b, t) go to cache row len[b] + t,
+//                      for t < n[b] and len[b] + t < Tmax; every other cache byte is untouched.
+//   attn_extend_k      grid (ceil(T / 32), B * H): one workgroup per (32-query tile, b, h).
+//
+// attn_extend_k follows the 32x32x16 forward of attention.hip (attn_fwd3_k): S^T = K Q^T with
+// the query on the lane (C/D column) and the keys in the 16 registers, so the online softmax is
+// lane-local plus one exchange between lanes l and l ^ 32 (same query, other keys), and P^T
+// rounded to bf16 in registers is directly the B operand of O^T += V^T P^T; V^T comes from LDS
+// by ds_read_b64_tr_b16 with the matching k order.  What differs:
+//  * query (b, t) sees keys [0, len[b] + t]: the diagonal sits at the per-row offset len[b],
+//    read from DEVICE memory (no host synchronisation; len has 1 or B elements, as in decode);
+//  * query (b, t) is live iff t < n[b] (n null: T) and len[b] + t < Tmax; a query that is not
+//    live loads nothing and stores zeros.  Q rows of queries that are not live are replaced by
+//    zeros, masked scores are selected (not multiplied) away, and V rows past the tile's last
+//    attended key are staged as zeros, so NaN in padded q rows or in cache rows nobody attends
+//    cannot reach a live output;
+//  * the 4 waves of a workgroup share the 32 queries and take the 32-key tiles w, w + 4, ...
+//    (a short chunk over a long prefix still spreads its keys over the waves); key tiles wholly
+//    above the tile's diagonal are never visited.  Each wave stages its own V tile in its own
+//    LDS region (wave-local ordering only), and at the end the waves' (m, l, O) partials meet
+//    in LDS and are merged in wave order: deterministic, no atomics, no waiting between
+//    workgroups.
+#include "common.h"
+#include "../dpfs_api.h"
+#include "attn_common.h"
+
+namespace dpfs {
+
+constexpr int kExtQ = 32;    // queries per workgroup
+constexpr int kExtK = 32;    // keys per wave tile
+
+// 16-byte chunk swizzle of a wave's [32][HD] V tile: conflict-free for the transposed reads
+// (32 lanes = 4 rows x 64 B); hd 32 rows are one 64-B span, left as they are.
+template <int HD>
+__device__ __forceinline__ int ext_swz(int r, int ch) {
+  if (HD == 32) return ch;
+  return HD == 64 ? (ch ^ (((r >> 1) & 1) << 2)) : (ch ^ ((r & 3) << 2));
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q, long long ldq,
+                                                     const bf16* __restrict__ kc, const bf16* __restrict__ vc,
+                                                     const int* __restrict__ len_ptr, int len_rows,
+                                                     const int* __restrict__ n_ptr, bf16* __restrict__ o, int T,
+                                                     int H, int Tmax, float scale) {
+  constexpr int KS = HD / 16, DTN = HD / 32, RB = HD * 2, CPR = HD / 8;
+  constexpr int VT = kExtK * RB;             // a wave's V tile
+  constexpr int NVC = kExtK * CPR / 64;      // 16-byte V chunks per lane per tile
+  constexpr int OLD = HD + 4;                // padded fp32 row of the merge image
+  constexpr int MERGE = 4 * kExtQ * OLD * 4;
+  static_assert(4 * VT <= MERGE, "the V tiles alias the merge image");
+  __shared__ __attribute__((aligned(16))) char smem[MERGE];
+  __shared__ float ml_lds[4][kExtQ][2];
+
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int q0 = blockIdx.x * kExtQ;
+  const int wave = threadIdx.x >> 6, l = lane_id(), r32 = l & 31, hf = l >> 5, g16 = l >> 4, i16 = l & 15;
+  KASSERT(len_ptr[len_rows ? b : 0] >= 0, "cache length %d of sequence %d", len_ptr[len_rows ? b : 0], b);
+  const int len = len_ptr[len_rows ? b : 0];
+  const int nb = n_ptr ? min(max(n_ptr[b], 0), T) : T;
+  // live queries of this sequence: t < nlive
+  const int nlive = len < 0 ? 0 : min(nb, Tmax - len);
+  bf16* obase = o + ((long long)b * T) * ((long long)H * HD) + (long long)h * HD;
+
+  if (q0 >= nlive) {   // block-uniform: nothing to attend, the tile's rows are zeros
+    const int qq = threadIdx.x >> 3, part = threadIdx.x & 7;
+    if (q0 + qq < T) {
+      bf16* orow = obase + (long long)(q0 + qq) * H * HD + part * (HD / 8);
+      const bf16x4 z = {};
+#pragma unroll
+      for (int c = 0; c < HD / 32; ++c) *reinterpret_cast<bf16x4*>(orow + 4 * c) = z;
+    }
+    return;
+  }
+  const int kmax = len + min(q0 + kExtQ, nlive) - 1;   // last key any query of the tile attends (< Tmax)
+  const int nkt = kmax / kExtK + 1;
+  const float c2 = scale * kLog2e;
+
+  // Q^T operand: lane holds Q[q0 + r32][16 ks + 8 hf + j]; zeros for a query that is not live
+  const int tq = q0 + r32;
+  const bool live = tq < nlive;
+  bf16x8 qf[KS];
+  {
+    const bf16* qrow = q + ((long long)b * T + tq) * ldq + (long long)h * HD + 8 * hf;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      bf16x8 v = {};
+      if (live) v = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks);
+      qf[ks] = v;
+    }
+  }
+  // the last key of this lane's query, relative to its first key row of a tile (4 hf)
+  const int qlim = (live ? len + tq : -1) - 4 * hf;
+
+  const bf16* kbase = kc + ((long long)b * Tmax * H + h) * HD;
+  const bf16* vbase = vc + ((long long)b * Tmax * H + h) * HD;
+  const long long ldkv = (long long)H * HD;
+  char* lv = smem + wave * VT;
+  // V^T fragment reads (as attn_fwd3_k): rows 16 s + 4 hf + (i16 >> 2) [+ 8], d columns
+  // 32 dt + 16 (g16 & 1) + 4 (i16 & 3); the swizzle ignores the row bits the 16 s / + 8 steps move
+  int voff[DTN];
+#pragma unroll
+  for (int dt = 0; dt < DTN; ++dt) {
+    const int row = 4 * hf + (i16 >> 2);
+    const int col = 32 * dt + 16 * (g16 & 1) + 4 * (i16 & 3);
+    voff[dt] = row * RB + (ext_swz<HD>(row, col >> 3) << 4) + (col & 7) * 2;
+  }
+
+  bf16x8 kreg[KS];
+  u32x4 vreg[NVC];
+  // K fragment (A operand): lane holds K[k0 + r32][16 ks + 8 hf + j]; rows past kmax are masked
+  // after the product, so they may hold anything, but the address stays inside the cache.
+  // V rows past kmax are zeros: their P is 0, and 0 x NaN would not be.
+  auto fetch = [&](int kt) __attribute__((always_inline)) {
+    const int k0 = kt * kExtK;
+    const bf16* krow = kbase + (long long)min(k0 + r32, kmax) * ldkv + 8 * hf;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) kreg[ks] = *reinterpret_cast<const bf16x8*>(krow + 16 * ks);
+#pragma unroll
+    for (int i = 0; i < NVC; ++i) {
+      const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (k0 + r <= kmax) v = *reinterpret_cast<const u32x4*>(vbase + (long long)(k0 + r) * ldkv + ch * 8);
+      vreg[i] = v;
+    }
+  };
+
+  f32x16 oacc[DTN];
+#pragma unroll
+  for (int d = 0; d < DTN; ++d)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) oacc[d][i] = 0.f;
+  float m = -INFINITY, lsum = 0.f;
+
+  if (wave < nkt) fetch(wave);
+  for (int kt = wave; kt < nkt; kt += 4) {
+    const int k0 = kt * kExtK;
+    // this tile's V into the wave's LDS region (the wave's earlier reads of it have returned:
+    // their values fed the MFMAs above); LDS serves a wave's operations in order
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < NVC; ++i) {
+      const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
+      *reinterpret_cast<u32x4*>(lv + r * RB + (ext_swz<HD>(r, ch) << 4)) = vreg[i];
+    }
+    bf16x8 kcur[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) kcur[ks] = kreg[ks];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (kt + 4 < nkt) fetch(kt + 4);   // the next tile's loads fly under this tile's math
+
+    f32x16 s;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) s = MFMA32(kcur[ks], qf[ks], s);
+    // key k0 + 8 (i >> 2) + 4 hf + (i & 3) is attended iff it is <= len + tq
+    const bool need_mask = k0 + kExtK - 1 > len + q0 || q0 + kExtQ > nlive;   // wave-uniform
+    if (need_mask) {
+      const int lim = qlim - k0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = (8 * (i >> 2) + (i & 3) > lim) ? -INFINITY : s[i];
+    }
+    float mx = s[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
+    mx = pair_max(mx) * c2;                     // both lanes of a query move m together
+    const float mnew = fmaxf(m, mx);
+    const float ms = mnew == -INFINITY ? 0.f : mnew;   // no key yet: p = exp2(-inf) = 0
+    const float alpha = __builtin_amdgcn_exp2f(m - ms);
+    m = mnew;
+    lsum *= alpha;
+#pragma unroll
+    for (int d = 0; d < DTN; ++d) oacc[d] *= alpha;
+    float ps = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], c2, -ms));
+      ps += s[i];
+    }
+    lsum += ps;
+    bf16x8 pk[2];
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pk[k2][j] = (bf16)s[8 * k2 + j];
+    // O^T[d][q] += V^T[d][k] P^T[k][q]
+#pragma unroll
+    for (int dt = 0; dt < DTN; ++dt)
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) {
+        const char* vb = lv + voff[dt] + 16 * k2 * RB;
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)vb);
+        const s16x4 hi =
+            __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vb + 8 * RB));
+        oacc[dt] = MFMA32(tr_join(lo, hi), pk[k2], oacc[dt]);
+      }
+  }
+
+  // the waves' partials meet in LDS (the V tiles are dead once every wave is past its loop)
+  __syncthreads();
+  {
+    const float ls = pair_sum(lsum);
+    float* orow = reinterpret_cast<float*>(smem) + ((long long)wave * kExtQ + r32) * OLD;
+#pragma unroll
+    for (int dt = 0; dt < DTN; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 v = {oacc[dt][4 * g], oacc[dt][4 * g + 1], oacc[dt][4 * g + 2], oacc[dt][4 * g + 3]};
+        *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * hf) = v;
+      }
+    if (hf == 0) {
+      ml_lds[wave][r32][0] = m;
+      ml_lds[wave][r32][1] = ls;
+    }
+  }
+  __syncthreads();
+  // merge in wave order; thread = (query, HD / 8 output columns)
+  {
+    const int qq = threadIdx.x >> 3, part = threadIdx.x & 7;
+    const int t = q0 + qq;
+    if (t >= T) return;
+    float M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) M = fmaxf(M, ml_lds[w][qq][0]);
+    float f[4], ls = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float mw = ml_lds[w][qq][0];
+      f[w] = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
+      ls += f[w] * ml_lds[w][qq][1];
+    }
+    const bool lq = t < nlive;
+    const float inv = lq ? 1.f / ls : 0.f;
+    bf16* orow = obase + (long long)t * H * HD + part * (HD / 8);
+#pragma unroll
+    for (int c = 0; c < HD / 32; ++c) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem) +
+                                                        ((long long)w * kExtQ + qq) * OLD + part * (HD / 8) + 4 * c);
+        acc += f[w] * v;
+      }
+      bf16x4 r = {};
+      if (lq) r = (bf16x4){(bf16)(acc[0] * inv), (bf16)(acc[1] * inv), (bf16)(acc[2] * inv), (bf16)(acc[3] * inv)};
+      *reinterpret_cast<bf16x4*>(orow + 4 * c) = r;
+    }
+  }
+}
+
+// cache[b, len[b] + t, h, :] = the k / v parts of packed row b * T + t, for t < n[b] (n null: T)
+// and len[b] + t < Tmax.  One 16-byte vector per thread step.
+__global__ __launch_bounds__(256) void kv_append_chunk_k(const bf16* __restrict__ ksrc, const bf16* __restrict__ vsrc,
+                                                         long long ld, bf16* __restrict__ kc, bf16* __restrict__ vc,
+                                                         const int* __restrict__ len_ptr, int len_rows,
+                                                         const int* __restrict__ n_ptr, int B, int T, int H, int HD,
+                                                         int Tmax) {
+  const int nv = H * HD / 8;               // 16-byte vectors per token row
+  const long long per = (long long)B * T * nv;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * per;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int isv = i >= per;
+    const long long j = isv ? i - per : i;
+    const int c = (int)(j % nv);
+    const long long row = j / nv;          // b * T + t
+    const int b = (int)(row / T), t = (int)(row % T);
+    const int len = len_ptr[len_rows ? b : 0];
+    KASSERT(len >= 0, "cache length %d of sequence %d", len, b);
+    const int nb = n_ptr ? n_ptr[b] : T;
+    if (len < 0 || t >= nb || len + t >= Tmax) continue;
+    const bf16* src = (isv ? vsrc : ksrc) + row * ld + 8 * c;
+    bf16* dst = (isv ? vc : kc) + ((long long)b * Tmax + len + t) * H * HD + 8 * c;
+    *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+  }
+}
+
+}  // namespace dpfs
+
+using namespace dpfs;
+
+// q: bf16 rows (B * T, >= H * HD) with row stride ldq (a multiple of 8); kc / vc: contiguous
+// (B, Tmax, H, HD) caches that already hold the chunk's rows; len: 1 (len_rows 0) or B
+// (len_rows 1) device int32, the cache length before the chunk; n: B device int32 or null (T
+// for every row); o: (B * T, H * HD) contiguous.  HD is 32, 64 or 128.
+extern "C" void dpfs_attn_extend(const void* q, long long ldq, const void* kc, const void* vc, const int* len,
+                                 int len_rows, const int* n, void* o, int B, int T, int H, int HD, int Tmax,
+                                 float scale, hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H);
+#define EXT_LAUNCH(HD_)                                                                                         \
+  attn_extend_k<HD_><<<grid, 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, len, len_rows, n, \
+                                          (bf16*)o, T, H, Tmax, scale)
+  if (HD == 32) EXT_LAUNCH(32);
+  else if (HD == 64) EXT_LAUNCH(64);
+  else EXT_LAUNCH(128);
+#undef EXT_LAUNCH
+}
+
+// ksrc / vsrc: the k / v parts of the packed rows (B * T rows of stride ld); len, len_rows, n as
+// in dpfs_attn_extend.
+extern "C" void dpfs_kv_append_chunk(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc,
+                                     const int* len, int len_rows, const int* n, int B, int T, int H, int HD,
+                                     int Tmax, hipStream_t s) {
+  const long long total = 2LL * B * T * (H * HD / 8);
+  const int grid = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  if (total > 0)
+    kv_append_chunk_k<<<grid, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kc, (bf16*)vc, len,
+                                           len_rows, n, B, T, H, HD, Tmax);
+}

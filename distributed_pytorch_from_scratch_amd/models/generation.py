@@ -6,6 +6,10 @@ for the local head shard:
 
 * prefill: the prompt goes through the causal flash-attention kernel and fills cache rows
   ``[0, T0)``;
+* prefill against a cache: T > 1 new tokens after what the cache holds (a prompt fed in pieces,
+  ``prefill_chunk``; a multi-token continuation, also of a ragged cache) append their keys /
+  values at every row's own length (``_kv_append_chunk``) and attend the cached prefix plus the
+  causal part of the chunk (``_attn_extend``, csrc/kernels/attn_extend.hip);
 * decode: one token per sequence per step.  The step is written against DEVICE state only —
   the cache length ``cache.len_t`` (int32) and the position ids ``pos`` live on the GPU, the
   new key/value rows are appended at ``len_t`` (``kv_append``), the single-query split-K
@@ -101,34 +105,62 @@ class KVCache:
         return self.len_t.long().expand(B).contiguous()
 
 
-def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int, T: int):
-    """Multi-token step (prefill, or T > 1 continuation) with host-side cache bookkeeping."""
+def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int, T: int, n_t=None):
+    """Multi-token step (prefill, or T > 1 continuation) with host-side cache bookkeeping.  The
+    continuation (``cache.len > 0``) reads the cache lengths from ``cache.len_t`` (the caller has
+    run ``cache.sync_device_len()``); ``n_t`` (device int32 (B,), or None for T) gives the real
+    new tokens of every right-padded row."""
     attn = layer.attn
     h, hd = attn.num_local_heads, attn.head_dim
     qkv = attn.wqkv(x2d)                                     # (B*T, 3*h*hd)
     k_ = K(qkv)
     k_.rope_(qkv, positions, tab, 2 * h, hd, False)
-    q = qkv[:, : h * hd].view(B, T, h, hd)
-    kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
-    v = qkv[:, 2 * h * hd:].view(B, T, h, hd)
-    t0 = cache.len
-    cache.k[li][:, t0:t0 + T] = kk
-    cache.v[li][:, t0:t0 + T] = v
     scale = 1.0 / math.sqrt(hd)
-    if t0 == 0:
+    if cache.len == 0:
         # prefill: causal flash attention over the prompt
+        q = qkv[:, : h * hd].view(B, T, h, hd)
+        kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
+        v = qkv[:, 2 * h * hd:].view(B, T, h, hd)
+        cache.k[li][:, :T] = kk
+        cache.v[li][:, :T] = v
         o, _ = k_.attn_fwd(q, kk, v, scale, True)
     else:
-        # T new queries against every cached key (continuation chunk)
-        keys = cache.k[li][:, : t0 + T].float()             # (B, S, h, hd)
-        vals = cache.v[li][:, : t0 + T].float()
-        s = torch.einsum("bthd,bshd->bhts", q.float(), keys) * scale
-        S = t0 + T
-        mask = torch.ones(T, S, dtype=torch.bool, device=s.device).triu(S - T + 1)
-        s = s.masked_fill(mask, float("-inf"))
-        p = torch.softmax(s, dim=-1)
-        o = torch.einsum("bhts,bshd->bthd", p, vals).to(q.dtype)
+        # continuation chunk: every row appends its new keys / values at its own cache length,
+        # then its T new queries attend the cached prefix plus the causal part of the chunk
+        k_._kv_append_chunk(qkv, cache.k[li], cache.v[li], cache.len_t, n_t)
+        o = k_._attn_extend(qkv, cache.k[li], cache.v[li], cache.len_t, n_t, scale)
     return attn.wo(o.reshape(B * T, h * hd))
+
+
+def _prefill_piece(model, ids: torch.Tensor, cache: KVCache, n: Optional[List[int]]) -> torch.Tensor:
+    """Feed ``ids`` (B, T) after what the cache holds and advance its host lengths; ``n`` gives
+    the real ids of every right-padded row (0..T, ragged caches), None means T.  Returns the
+    hidden states (B, T, D) in front of the final norm."""
+    B, T = ids.shape
+    dev = ids.device
+    dt = model.act_dtype(dev)
+    model.embedding.out_dtype = dt
+    x = model.embedding(ids).reshape(B * T, -1).to(dt)
+    n_t = None
+    if cache.len == 0:
+        positions = torch.arange(T, device=dev).repeat(B)
+    else:
+        cache.sync_device_len()
+        base = cache.lens if cache.ragged else [cache.len] * B
+        # (the padding and rows past the capacity stay inside the RoPE table)
+        positions = (torch.tensor(base, device=dev)[:, None] + torch.arange(T, device=dev)).clamp(
+            max=cache.t_max - 1).reshape(-1)
+        if n is not None:
+            n_t = torch.tensor(n, dtype=torch.int32, device=dev)
+    tab = model.rope_table(dev)
+    for li, layer in enumerate(model.layers):
+        x = x + _attention_step(layer, layer.norm1(x), positions, tab, cache, li, B, T, n_t)
+        x = x + layer.ffn(layer.norm2(x))
+    if cache.ragged:
+        cache.set_lens(c + m for c, m in zip(cache.lens, n if n is not None else [T] * B))
+    else:
+        cache.len += T
+    return x.view(B, T, -1)
 
 
 def _check_lens(lens, B: int, T: int) -> List[int]:
@@ -141,43 +173,53 @@ def _check_lens(lens, B: int, T: int) -> List[int]:
 
 
 @torch.inference_mode()
-def logits_step(model, ids: torch.Tensor, cache: KVCache, lens=None) -> torch.Tensor:
+def logits_step(model, ids: torch.Tensor, cache: KVCache, lens=None, prefill_chunk: int = 0) -> torch.Tensor:
     """Feed ``ids`` (B, T) at positions cache.len.., return (B, vocab) logits of the last one.
 
-    ``lens`` (B ints in [1, T]) prefills a ragged cache with a right-padded prompt: row b holds
-    ``lens[b]`` real ids, the logits are those of its last real id, and its cache length becomes
-    ``lens[b]`` (the cache rows of the padding are overwritten by the appends before any read).
-    Later single-token steps on that cache advance every row at its own length."""
+    ``lens`` (B ints in [1, T]) feeds a ragged cache right-padded rows: row b holds ``lens[b]``
+    real ids, the logits are those of its last real id, and its cache length grows by
+    ``lens[b]`` (the cache rows of a prefill's padding are overwritten by the appends before any
+    read; a continuation appends the real ids only).  A multi-token continuation of a ragged
+    cache needs ``lens``.  Later single-token steps on that cache advance every row at its own
+    length.
+
+    ``prefill_chunk`` > 0 feeds ``ids`` in pieces of at most that many tokens (the first piece of
+    an empty cache through the flash prefill, the others through ``_attn_extend``), so the
+    activations of a call scale with the piece and not with T; the logits are still those of
+    every row's last real id."""
     B, T = ids.shape
     dev = ids.device
-    dt = model.act_dtype(dev)
+    if prefill_chunk < 0:
+        raise ValueError(f"logits_step: prefill_chunk must be >= 0, got {prefill_chunk}")
     if lens is not None:
         if not cache.ragged:
             raise ValueError("logits_step: lens needs a KVCache(..., ragged=True)")
         lens = _check_lens(lens, B, T)
-    if cache.ragged and T > 1 and cache.len > 0:
-        raise ValueError("logits_step: a multi-token continuation of a ragged cache is not supported")
-    assert cache.len + T <= cache.t_max <= model.args.maxlen
+    if cache.ragged and T > 1 and cache.len > 0 and lens is None:
+        raise ValueError("logits_step: a multi-token continuation of a ragged cache is not supported "
+                         "without lens (the real new ids of every row)")
+    if cache.ragged and cache.len > 0 and lens is not None:
+        assert all(c + m <= cache.t_max for c, m in zip(cache.lens, lens)) and cache.t_max <= model.args.maxlen
+    else:
+        assert cache.len + T <= cache.t_max <= model.args.maxlen
     if T == 1 and cache.len > 0:
         cache.sync_device_len()
         pos = cache.device_pos() if cache.ragged else torch.full((B,), cache.len, dtype=torch.int64, device=dev)
         _, logits = decode_step(model, ids, pos, cache)
         cache.advance()
         return logits
-    model.embedding.out_dtype = dt
-    x = model.embedding(ids).reshape(B * T, -1).to(dt)
-    positions = torch.arange(cache.len, cache.len + T, device=dev).repeat(B)
-    tab = model.rope_table(dev)
-    for li, layer in enumerate(model.layers):
-        x = x + _attention_step(layer, layer.norm1(x), positions, tab, cache, li, B, T)
-        x = x + layer.ffn(layer.norm2(x))
-    if cache.ragged:
-        cache.set_lens(lens if lens is not None else [T] * B)
-        last = torch.tensor(cache.lens, device=dev) - 1       # the last real id of every row
-        h = model.norm(x.view(B, T, -1)[torch.arange(B, device=dev), last].contiguous())
-    else:
-        cache.len += T
-        h = model.norm(x.view(B, T, -1)[:, -1].contiguous())
+    step = prefill_chunk if 0 < prefill_chunk < T else T
+    last = [m - 1 for m in (lens if lens is not None else [T] * B)]   # the last real id of every row
+    h = None
+    for s in range(0, T, step):
+        e = min(s + step, T)
+        n = [min(max(m + 1 - s, 0), e - s) for m in last] if cache.ragged else None
+        x = _prefill_piece(model, ids[:, s:e].contiguous(), cache, n)
+        rows = [b for b, m in enumerate(last) if s <= m < e]      # their last real id is in this piece
+        if rows:
+            h = x.new_empty(B, x.size(-1)) if h is None else h
+            h[rows] = x[rows, [last[b] - s for b in rows]]
+    h = model.norm(h)
     logits = model._lm_head_local(h)
     logits = comm_ops.Gather.apply(logits, model.lm_head.sizes)
     return logits[..., : model.vocab_size].float()
@@ -389,7 +431,7 @@ def clear_sessions():
 @torch.inference_mode()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
              max_len: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-             seed: int = 0, prompt_lens=None) -> List[List[int]]:
+             seed: int = 0, prompt_lens=None, prefill_chunk: int = 0) -> List[List[int]]:
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -405,7 +447,13 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     ``sample_logits``: softmax(logits / temperature) cut to the ``top_k`` largest logits (0:
     off) and then to the ``top_p`` nucleus (1: off), ties at either cutoff kept whole.  The draw
     for the token that follows position t of row b depends only on (``seed``, b, t), so the same
-    call returns the same tokens on the graph and the eager path and on every TP rank."""
+    call returns the same tokens on the graph and the eager path and on every TP rank.
+
+    ``prefill_chunk`` > 0 prefills the prompt in pieces of at most that many tokens
+    (``logits_step``): the peak activation memory of the call then scales with the piece, not
+    with T0.  The decode steps, graphs and sessions are the same; 0 prefills the prompt whole."""
+    if prefill_chunk < 0:
+        raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
                          f"{temperature}, {top_k}, {top_p}")
@@ -414,14 +462,14 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     dev = prompt.device
     if prompt_lens is not None:
         return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
-                                sample)
+                                sample, prefill_chunk)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev)
     out = [list(map(int, row)) for row in prompt.tolist()]
     done = [False] * B
     if max_new_tokens <= 0 or T0 >= t_max:
         return out
-    logits = logits_step(model, prompt, cache)
+    logits = logits_step(model, prompt, cache, prefill_chunk=prefill_chunk)
     if sample is None:
         nxt = logits.argmax(-1)
     else:   # the first token follows position T0 - 1
@@ -470,7 +518,8 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
                 return out
 
 
-def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample):
+def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
+                     prefill_chunk: int = 0):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
     that has filled the cache frozen inside it (``_step_advance_rows``)."""
@@ -487,7 +536,8 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     # The padded prompt up to the longest row that fits the cache; a row at or past the cache
     # capacity is done already and enters the cache full (frozen).
     T = min(max(lens), t_max)
-    logits = logits_step(model, prompt[:, :T].contiguous(), cache, [min(n, T) for n in lens])
+    logits = logits_step(model, prompt[:, :T].contiguous(), cache, [min(n, T) for n in lens],
+                         prefill_chunk)
     if sample is None:
         nxt = logits.argmax(-1)
     else:   # the first token of row b follows position lens[b] - 1

@@ -98,6 +98,8 @@ kv_append = reference.kv_append
 rope_append = reference.rope_append
 step_advance = reference.step_advance
 _step_advance_rows = reference._step_advance_rows
+_attn_extend = reference._attn_extend
+_kv_append_chunk = reference._kv_append_chunk
 gemv_nt = reference.gemv_nt
 
 

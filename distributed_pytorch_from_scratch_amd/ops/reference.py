@@ -234,6 +234,54 @@ def kv_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     v_cache[:, t] = qkv[:, 2 * H * hd: 3 * H * hd].view(B, H, hd).to(v_cache.dtype)
 
 
+def _chunk_rows(len: torch.Tensor, n: Optional[torch.Tensor], B: int, T: int, Tmax: int):
+    """Per sequence (cache length before the chunk, live new tokens): token t of row b is live
+    iff t < n[b] (``n`` None: T) and len[b] + t < T_max."""
+    assert len.numel() in (1, B), "len must have 1 or B elements"
+    assert n is None or n.numel() == B, "n must have B elements"
+    lens = len.reshape(-1).expand(B).tolist()
+    ns = [T] * B if n is None else n.reshape(-1).tolist()
+    return [(L, 0 if L < 0 else max(0, min(m, T, Tmax - L))) for L, m in zip(lens, ns)]
+
+
+def _kv_append_chunk(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, len: torch.Tensor,
+                     n: Optional[torch.Tensor] = None) -> None:
+    """The multi-row kv_append: the k / v parts of packed row b*T + t of qkv [B*T, 3*H*hd] go to
+    cache row len[b] + t, for t < n[b] (``n`` None: T) and len[b] + t < T_max; every other cache
+    element is left as it is."""
+    B, Tmax, H, hd = k_cache.shape
+    T = qkv.size(0) // B
+    rows = qkv.view(B, T, -1)
+    for b, (L, m) in enumerate(_chunk_rows(len, n, B, T, Tmax)):
+        if m > 0:
+            k_cache[b, L:L + m] = rows[b, :m, H * hd: 2 * H * hd].view(m, H, hd).to(k_cache.dtype)
+            v_cache[b, L:L + m] = rows[b, :m, 2 * H * hd: 3 * H * hd].view(m, H, hd).to(v_cache.dtype)
+
+
+def _attn_extend(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, len: torch.Tensor,
+                 n: Optional[torch.Tensor], scale: float) -> torch.Tensor:
+    """A chunk of T new queries per sequence against the cache (which already holds the chunk's
+    keys and values, ``_kv_append_chunk``): q [B*T, >= H*hd] rows, row b*T + t = new token t of
+    sequence b; it attends cache rows [0, len[b] + t].  A token with t >= n[b] (``n`` None: T)
+    or len[b] + t >= T_max reads nothing and gives zeros.  fp32 math, any cache dtype.  Returns
+    o [B*T, H*hd] in q.dtype."""
+    B, Tmax, H, hd = k_cache.shape
+    T = q.size(0) // B
+    qf = q[:, : H * hd].float().view(B, T, H, hd)
+    o = torch.zeros(B, T, H, hd, dtype=torch.float32, device=q.device)
+    for b, (L, m) in enumerate(_chunk_rows(len, n, B, T, Tmax)):
+        if m == 0:
+            continue
+        S = L + m
+        keys = k_cache[b, :S].float()                        # (S, H, hd)
+        vals = v_cache[b, :S].float()
+        s = torch.einsum("thd,shd->hts", qf[b, :m], keys) * scale
+        mask = torch.ones(m, S, dtype=torch.bool, device=s.device).triu(L + 1)
+        p = torch.softmax(s.masked_fill(mask, float("-inf")), dim=-1)
+        o[b, :m] = torch.einsum("hts,shd->thd", p, vals)
+    return o.view(B * T, H * hd).to(q.dtype)
+
+
 def gemv_nt_ok(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> bool:
     return True
 

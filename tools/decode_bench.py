@@ -4,6 +4,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
     python tools/decode_bench.py [--model gpt2-small] [--batch 1 8] [--prompt 128] [--new 256]
                                  [--temperature T --top_k K --top_p P] [--repeats R] [--sample-kernel]
                                  [--ragged | --ragged-equal]
+                                 [--prefill-chunk N [N ...]] [--continuation --t0 1024 --chunk 256]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -17,6 +18,14 @@ kernels): the prompt lengths of a batch are spread evenly over [prompt/4, prompt
 "one-by-one" line times the same prompts decoded one after the other at batch 1 (uniform path,
 each with its session warm).  ``--ragged-equal`` runs the per-row path with every length =
 ``--prompt``: against the plain run, the price of the per-row length loads.
+
+``--prefill-chunk N [N ...]`` times the prefill alone (``logits_step`` of a ``--prompt``-id prompt
+up to the first token's logits: time to first token) whole and in pieces of each N, with the
+peak allocation above the cache (``max_memory_allocated``).  ``--continuation`` times one
+``--chunk``-token continuation of a cache that holds ``--t0`` ids, on the kernels
+(``_kv_append_chunk`` + ``_attn_extend``) and on the framework formulation they replaced (slice
+assignment, fp32 einsum / softmax / einsum over the whole cache), in interleaved rounds
+(``--repeats`` of them) with the medians.
 """
 from __future__ import annotations
 
@@ -44,6 +53,10 @@ def main():
     ap.add_argument("--sample-kernel", action="store_true", help="time the sample_logits launch alone")
     ap.add_argument("--ragged", action="store_true", help="ragged batch: lengths spread over [prompt/4, prompt]")
     ap.add_argument("--ragged-equal", action="store_true", help="per-row path with all lengths = prompt")
+    ap.add_argument("--prefill-chunk", type=int, nargs="+", default=None, help="time the prefill whole and in pieces")
+    ap.add_argument("--continuation", action="store_true", help="time one multi-token continuation")
+    ap.add_argument("--t0", type=int, default=1024, help="--continuation: ids in the cache")
+    ap.add_argument("--chunk", type=int, default=256, help="--continuation: new ids")
     a = ap.parse_args()
     sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
     import torch
@@ -54,11 +67,17 @@ def main():
     os.environ.setdefault("MASTER_PORT", "29591")
     init_dist_env(rank=0, tp_size=1, world_size=1)
     args = get_preset(a.model)
+    if a.continuation and a.t0 + a.chunk > args.maxlen:     # the RoPE table must cover the continuation
+        args = get_preset(a.model, maxlen=a.t0 + a.chunk)
     m = Transformer.from_args(args).cuda()
     m.reset_parameters()
     m.eval()
     if a.sample_kernel:
         return sample_kernel_bench(a, m.lm_head.weight.size(0), args.vocab_size)
+    if a.continuation:
+        return continuation_bench(a, m)
+    if a.prefill_chunk:
+        return prefill_bench(a, m)
     for B in a.batch:
         prompt = torch.randint(0, args.vocab_size, (B, a.prompt), device="cuda")
         lens = None
@@ -119,6 +138,119 @@ def main():
         print(json.dumps({"model": a.model, "batch": B, "mode": "full-recompute", "prompt": a.prompt,
                           "new": a.recompute_new, "ms_per_step": round(1000 * dt / a.recompute_new, 3),
                           "tokens_per_s": round(B * a.recompute_new / dt, 1)}), flush=True)
+
+
+def _new_cache(m, B, t_max):
+    import torch
+    from distributed_pytorch_from_scratch_amd.models.generation import KVCache
+    attn = m.layers[0].attn
+    return KVCache(len(m.layers), B, t_max, attn.num_local_heads, attn.head_dim, torch.bfloat16, torch.device("cuda"))
+
+
+def _timed(fn):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return 1000 * (time.perf_counter() - t0)
+
+
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def prefill_bench(a, m):
+    """Time to first token (ms) and peak bytes above the cache of the prefill of ``--prompt`` ids,
+    whole (chunk 0) and in pieces, in interleaved rounds; one JSON line per (batch, chunk)."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.models.generation import logits_step
+    chunks = [0] + [c for c in a.prefill_chunk if c > 0]
+    for B in a.batch:
+        prompt = torch.randint(0, m.args.vocab_size, (B, a.prompt), device="cuda")
+        cache = _new_cache(m, B, a.prompt)
+        ms = {c: [] for c in chunks}
+        peak = {}
+
+        def run(c):
+            cache.reset()
+            return logits_step(m, prompt, cache, prefill_chunk=c).argmax(-1)
+
+        for c in chunks:                                    # warm-up: GEMM choices per piece shape
+            run(c)
+        for _ in range(a.repeats):
+            for c in chunks:
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                ms[c].append(_timed(lambda: run(c)))
+                peak[c] = torch.cuda.max_memory_allocated() - base
+        for c in chunks:
+            print(json.dumps({"bench": "prefill", "model": a.model, "batch": B, "prompt": a.prompt, "prefill_chunk": c,
+                              "ttft_ms": [round(x, 3) for x in ms[c]], "ttft_ms_median": round(_median(ms[c]), 3),
+                              "peak_bytes_above_cache": peak[c]}), flush=True)
+
+
+def continuation_bench(a, m):
+    """One ``--chunk``-token continuation at cache length ``--t0``: the kernel path against the
+    framework formulation it replaced, in interleaved rounds; one JSON line per batch."""
+    import math
+    import torch
+    from distributed_pytorch_from_scratch_amd.models import generation as G
+    from distributed_pytorch_from_scratch_amd.ops.dispatch import K
+
+    kernel_step = G._attention_step
+
+    def einsum_step(layer, x2d, positions, tab, cache, li, B, T, n_t=None):
+        """The continuation as it ran before the kernels: host offset, fp32 copies of the whole
+        cache, a materialised (B, H, T, S) score tensor."""
+        attn = layer.attn
+        h, hd = attn.num_local_heads, attn.head_dim
+        qkv = attn.wqkv(x2d)
+        K(qkv).rope_(qkv, positions, tab, 2 * h, hd, False)
+        q = qkv[:, : h * hd].view(B, T, h, hd)
+        t0 = cache.len
+        cache.k[li][:, t0:t0 + T] = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
+        cache.v[li][:, t0:t0 + T] = qkv[:, 2 * h * hd:].view(B, T, h, hd)
+        keys = cache.k[li][:, : t0 + T].float()
+        vals = cache.v[li][:, : t0 + T].float()
+        s = torch.einsum("bthd,bshd->bhts", q.float(), keys) * (1.0 / math.sqrt(hd))
+        S = t0 + T
+        mask = torch.ones(T, S, dtype=torch.bool, device=s.device).triu(S - T + 1)
+        p = torch.softmax(s.masked_fill(mask, float("-inf")), dim=-1)
+        o = torch.einsum("bhts,bshd->bthd", p, vals).to(q.dtype)
+        return attn.wo(o.reshape(B * T, h * hd))
+
+    for B in a.batch:
+        ids = torch.randint(0, m.args.vocab_size, (B, a.t0 + a.chunk), device="cuda")
+        cache = _new_cache(m, B, a.t0 + a.chunk)
+        G.logits_step(m, ids[:, : a.t0].contiguous(), cache)
+        new = ids[:, a.t0:].contiguous()
+        out = {}
+
+        def run(mode):
+            cache.len = a.t0                                # the same continuation again
+            G._attention_step = kernel_step if mode == "kernel" else einsum_step
+            try:
+                out[mode] = G.logits_step(m, new, cache)
+            finally:
+                G._attention_step = kernel_step
+
+        ms = {"kernel": [], "einsum": []}
+        for mode in ms:
+            run(mode)                                       # warm-up
+        rel = ((out["kernel"] - out["einsum"]).norm() / out["einsum"].norm()).item()
+        for _ in range(a.repeats):
+            for mode in ms:
+                ms[mode].append(_timed(lambda: run(mode)))
+        print(json.dumps({"bench": "continuation", "model": a.model, "batch": B, "t0": a.t0, "chunk": a.chunk,
+                          "kernel_ms": [round(x, 3) for x in ms["kernel"]],
+                          "einsum_ms": [round(x, 3) for x in ms["einsum"]],
+                          "kernel_ms_median": round(_median(ms["kernel"]), 3),
+                          "einsum_ms_median": round(_median(ms["einsum"]), 3),
+                          "kernel_not_slower_in_any_round": all(k <= e for k, e in zip(ms["kernel"], ms["einsum"])),
+                          "logits_rel_diff": rel}), flush=True)
 
 
 def sample_kernel_bench(a, ld: int, vocab: int):
