@@ -218,19 +218,19 @@ def _exp_terms(g):
     return 4 + g.abs()
 
 
-def ref_swiglu_fwd(gu, perm=False):
-    """(h, unit, fp32 term): h = silu(gate) up; unit = one bf16 rounding + the fp32 evaluation's
-    terms."""
+def ref_swiglu_fwd(gu, perm=False, bf16_out=True):
+    """(h, unit, fp32 term): h = silu(gate) up; unit = one rounding at the store (bf16, or fp32
+    with ``bf16_out`` off: fp32 storage) + the fp32 evaluation's terms."""
     g, u = gu_unperm64(gu, perm)
     h = g * torch.sigmoid(g) * u
     acc = (_exp_terms(g) + 3) * U32 * h.abs()
-    return h, U16 * h.abs() + acc, acc
+    return h, (U16 if bf16_out else U32) * h.abs() + acc, acc
 
 
-def ref_swiglu_bwd(dh64, gu, perm=False, dh_unit=None):
+def ref_swiglu_bwd(dh64, gu, perm=False, dh_unit=None, bf16_out=True):
     """(dgu natural layout, unit, fp32 term, column sums, their unit).  ``dh_unit``: an error
     bound of dh64's elements (the fused epilogue's dh is a bf16-rounded GEMM result), propagated
-    through the derivative."""
+    through the derivative.  ``bf16_out`` off: fp32 storage, the store rounds to fp32."""
     g, u = gu_unperm64(gu, perm)
     s = torch.sigmoid(g)
     kg = u * s * (1 + g * (1 - s))
@@ -242,7 +242,7 @@ def ref_swiglu_bwd(dh64, gu, perm=False, dh_unit=None):
     acc = et * U32 * mag
     if dh_unit is not None:
         acc = acc + torch.cat([dh_unit * kg.abs(), dh_unit * ku.abs()], -1)
-    unit = U16 * ref.abs() + acc
+    unit = (U16 if bf16_out else U32) * ref.abs() + acc
     M = ref.size(0)
     return ref, unit, acc, ref.sum(0), unit.sum(0) + (M + 1) * U32 * ref.abs().sum(0)
 
@@ -285,23 +285,25 @@ def ref_rmsnorm_bwd(dy, x, w, eps, dres=None, bf16_out=True):
     return dx, udx, dw, udw
 
 
-def ref_bias_residual(y, bias, res):
-    """(x, unit, fp32 term) of x = y + bias + res, fp32 adds, one rounding to bf16."""
+def ref_bias_residual(y, bias, res, bf16_out=True):
+    """(x, unit, fp32 term) of x = y + bias + res, fp32 adds, one rounding to bf16 (to fp32 with
+    ``bf16_out`` off: fp32 storage)."""
     y, res = d(y), d(res)
     ref, mag = y + res, y.abs() + res.abs()
     if bias is not None:
         ref, mag = ref + d(bias), mag + d(bias).abs()
     acc = 2 * U32 * mag
-    return ref, U16 * ref.abs() + acc, acc
+    return ref, (U16 if bf16_out else U32) * ref.abs() + acc, acc
 
 
-def ref_add_rmsnorm_fwd(y, bias, res, w, eps, x_kernel=None):
-    """The fused residual add + RMSNorm: x = y + bias + res rounded once to bf16, then the norm
-    of that ROUNDED x.  Returns (x, unit_x, h, unit_h, rstd, unit_rstd); h / rstd are taken from
-    ``x_kernel`` (the kernel's own x output) when given, else from the correctly rounded x."""
-    x, ux, _ = ref_bias_residual(y, bias, res)
-    xin = x_kernel if x_kernel is not None else x.to(torch.bfloat16)
-    h, uh, r, ur = ref_rmsnorm_fwd(xin, w, eps)
+def ref_add_rmsnorm_fwd(y, bias, res, w, eps, x_kernel=None, bf16_out=True):
+    """The fused residual add + RMSNorm: x = y + bias + res rounded once to bf16 (to fp32 with
+    ``bf16_out`` off: fp32 storage), then the norm of that ROUNDED x.  Returns (x, unit_x, h,
+    unit_h, rstd, unit_rstd); h / rstd are taken from ``x_kernel`` (the kernel's own x output)
+    when given, else from the correctly rounded x."""
+    x, ux, _ = ref_bias_residual(y, bias, res, bf16_out)
+    xin = x_kernel if x_kernel is not None else x.to(torch.bfloat16 if bf16_out else torch.float32)
+    h, uh, r, ur = ref_rmsnorm_fwd(xin, w, eps, bf16_out)
     return x, ux, h, uh, r, ur
 
 
@@ -806,7 +808,8 @@ def emb_ids(M, v_local, start, seed):
 
 def ref_embedding_bwd(dout, ids, v_local, start, acc=None):
     """(dw fp64 (v_local, D), unit): rows summed per id in fp64; unit (count + 1) U32 sum|rows|
-    (+ U32 |acc| with accumulate)."""
+    (+ U32 |acc| with accumulate).  The rows enter the fp32 sum unrounded whether dout is bf16 or
+    fp32, so the unit holds for both."""
     dd = d(dout)
     hit = (ids >= start) & (ids < start + v_local)
     loc = (ids - start)[hit]
@@ -838,7 +841,8 @@ def ref_ce_stats(logits, tgt, start, valid):
     grow, so the exponents' arguments telescope to max - x <= R (R = max - min of the row) and the
     argument roundings (the subtraction and the x log2 e inside __expf, U32 |argument| each) sum
     to 2 R U32; each level adds an __expf (3 ulp allowed), a product and an add: 5 U32; the
-    eight-term sum inside a vector 8 U32."""
+    eight-term sum inside a vector 8 U32.  Nothing assumes bf16 inputs: with fp32 logits a
+    vector holds four terms and a thread makes at most as many trips, so the same unit holds."""
     x = d(logits)[:, :valid]
     M = x.size(0)
     z = torch.zeros(M, dtype=torch.float64, device=x.device)
@@ -955,11 +959,12 @@ def ce_bwd_fp32(logits, tgt, lse, gs, start, valid, onehot_start=None):
 CE2_SEED = 19
 
 
-def ce2_inputs(M, V, shards, device="cpu", seed=CE2_SEED, all_ignored=False):
-    """Per shard of ``shards`` = [(vocab_start, valid), ...] bf16 logits (M, V), and the targets:
-    in every shard, beyond the last one (a valid row without a target logit), every seventh -1."""
+def ce2_inputs(M, V, shards, device="cpu", seed=CE2_SEED, all_ignored=False, dtype=torch.bfloat16):
+    """Per shard of ``shards`` = [(vocab_start, valid), ...] logits (M, V) of ``dtype`` (bf16, or
+    fp32 for the fp32 engine's storage), and the targets: in every shard, beyond the last one (a
+    valid row without a target logit), every seventh -1."""
     gen = torch.Generator().manual_seed(seed + V + len(shards))
-    logits = [(3 * torch.randn(M, V, generator=gen)).bfloat16().to(device) for _ in shards]
+    logits = [(3 * torch.randn(M, V, generator=gen)).to(dtype).to(device) for _ in shards]
     top = shards[-1][0] + shards[-1][1]
     tgt = torch.randint(0, top + 5, (M,), generator=gen)
     for i, (st, va) in enumerate(shards):
