@@ -164,6 +164,118 @@ void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torc
                                                     len.data_ptr<int>(), (int)B, (int)H, (int)hd, (int)Tmax, stream());
 }
 
+// ---------------------------------------------------------------------- fp8 KV cache --
+// e4m3 codes (B, T_max, H, hd) with one fp32 scale per (b, t, h) row (kernels/kv8.h).  Bound with
+// a leading underscore: the module's recorded public surface (tests/golden/ext_api.txt) is left
+// as it is.
+struct Q8Shape {
+  int64_t B, Tmax, H, hd;
+};
+
+Q8Shape check_cache_q8(const torch::Tensor& k8, const torch::Tensor& v8, const torch::Tensor& ks,
+                       const torch::Tensor& vs, const char* op) {
+  for (const torch::Tensor* c : {&k8, &v8}) {
+    check_cuda(*c, "fp8 cache");
+    TORCH_CHECK(c->dim() == 4 && c->is_contiguous() && c->scalar_type() == at::kFloat8_e4m3fn, op,
+                ": k8 / v8 must be contiguous float8_e4m3fn (B, T_max, H, hd) caches");
+  }
+  TORCH_CHECK(k8.sizes() == v8.sizes(), op, ": k8 / v8 shapes differ");
+  const Q8Shape s{k8.size(0), k8.size(1), k8.size(2), k8.size(3)};
+  for (const torch::Tensor* c : {&ks, &vs}) {
+    check_cuda(*c, "cache scales");
+    TORCH_CHECK(c->dim() == 3 && c->is_contiguous() && c->scalar_type() == torch::kFloat32 && c->size(0) == s.B &&
+                    c->size(1) == s.Tmax && c->size(2) == s.H && c->device() == k8.device(),
+                op, ": ks / vs must be contiguous fp32 (B, T_max, H) scales of the caches");
+  }
+  TORCH_CHECK(s.hd == 32 || s.hd == 64 || s.hd == 128, op, ": head_dim 32, 64 or 128");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(k8.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(v8.data_ptr()) % 16 == 0,
+              op, ": caches must be 16-byte aligned");
+  TORCH_CHECK(s.Tmax < (1LL << 30), op, ": shape too large");
+  return s;
+}
+
+// attn_decode over an fp8 cache.
+torch::Tensor attn_decode_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8, torch::Tensor ks, torch::Tensor vs,
+                             torch::Tensor len, double scale) {
+  check_rowmajor(q, "q");
+  const Q8Shape c = check_cache_q8(k8, v8, ks, vs, "attn_decode_q8");
+  const bool rows = check_len(len, c.B);
+  TORCH_CHECK(q.size(0) == c.B && q.size(1) >= c.H * c.hd && q.stride(0) % 8 == 0 &&
+                  q.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_decode_q8: q rows");
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({c.B, c.H * c.hd}, q.options());
+  const int ns = dpfs_decode_nsplit((int)c.Tmax);
+  auto part = torch::empty({c.B * c.H * ns * (c.hd + 2)}, q.options().dtype(torch::kFloat32));
+  dpfs_attn_decode_q8(q.data_ptr(), q.stride(0), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(),
+                      vs.data_ptr<float>(), len.data_ptr<int>(), rows ? 1 : 0, o.data_ptr(), c.H * c.hd,
+                      part.data_ptr<float>(), (int)c.B, (int)c.H, (int)c.hd, (int)c.Tmax, (float)scale, stream());
+  return o;
+}
+
+// attn_extend over an fp8 cache (which already holds the chunk's rows, _kv_append_chunk_q8).
+torch::Tensor attn_extend_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8, torch::Tensor ks, torch::Tensor vs,
+                             torch::Tensor len, c10::optional<torch::Tensor> n, double scale) {
+  check_rowmajor(q, "q");
+  const Q8Shape c = check_cache_q8(k8, v8, ks, vs, "attn_extend_q8");
+  const bool rows = check_len(len, c.B);
+  TORCH_CHECK(q.size(0) % c.B == 0 && q.size(0) >= c.B && q.size(1) >= c.H * c.hd && q.stride(0) % 8 == 0 &&
+                  q.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_extend_q8: q must be bf16 rows [B*T, >= H*hd], row stride % 8 == 0, 16-byte aligned");
+  const int64_t T = q.size(0) / c.B;
+  TORCH_CHECK(c.B * c.H <= 65535 && c.B * T * c.H * c.hd < (1LL << 31), "attn_extend_q8: shape too large");
+  const int* np = check_chunk_n(n, c.B, q);
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({c.B * T, c.H * c.hd}, q.options());
+  dpfs_attn_extend_q8(q.data_ptr(), q.stride(0), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(),
+                      vs.data_ptr<float>(), len.data_ptr<int>(), rows ? 1 : 0, np, o.data_ptr(), (int)c.B, (int)T,
+                      (int)c.H, (int)c.hd, (int)c.Tmax, (float)scale, stream());
+  return o;
+}
+
+// The quantising _kv_append_chunk: the k / v parts of packed qkv row b*T + t become codes and a
+// scale at cache row len[b] + t, for t < n[b] (n none: T) and len[b] + t < T_max; nothing else is
+// written.
+void kv_append_chunk_q8(torch::Tensor qkv, torch::Tensor k8, torch::Tensor v8, torch::Tensor ks, torch::Tensor vs,
+                        torch::Tensor len, c10::optional<torch::Tensor> n) {
+  check_rowmajor(qkv, "qkv");
+  const Q8Shape c = check_cache_q8(k8, v8, ks, vs, "kv_append_chunk_q8");
+  const bool rows = check_len(len, c.B);
+  TORCH_CHECK(qkv.size(0) % c.B == 0 && qkv.size(0) >= c.B && qkv.size(1) == 3 * c.H * c.hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "kv_append_chunk_q8: qkv must be [B*T, 3*H*hd] bf16, row stride % 8 == 0, 16-byte aligned");
+  const int64_t T = qkv.size(0) / c.B;
+  TORCH_CHECK(c.B * T * c.H * (c.hd / 8) < (1LL << 40), "kv_append_chunk_q8: shape too large");
+  const int* np = check_chunk_n(n, c.B, qkv);
+  const at::DeviceGuard g(qkv.device());
+  const char* p = static_cast<const char*>(qkv.data_ptr());
+  dpfs_kv_append_chunk_q8(p + c.H * c.hd * 2, p + 2 * c.H * c.hd * 2, qkv.stride(0), k8.data_ptr(), v8.data_ptr(),
+                          ks.data_ptr<float>(), vs.data_ptr<float>(), len.data_ptr<int>(), rows ? 1 : 0, np, (int)c.B,
+                          (int)T, (int)c.H, (int)c.hd, (int)c.Tmax, stream());
+}
+
+// rope_append into an fp8 cache: the rotation of rope_append, the rotated k row and the v row
+// quantised at *len / len[b].
+void rope_append_q8(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor k8, torch::Tensor v8,
+                    torch::Tensor ks, torch::Tensor vs, torch::Tensor len) {
+  check_rowmajor(qkv, "qkv");
+  const Q8Shape c = check_cache_q8(k8, v8, ks, vs, "rope_append_q8");
+  const bool rows = check_len(len, c.B);
+  TORCH_CHECK(qkv.size(0) == c.B && qkv.size(1) == 3 * c.H * c.hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "rope_append_q8: qkv must be [B, 3*H*hd] bf16, row stride % 8 == 0, 16-byte aligned");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == c.B,
+              "rope_append_q8: pos must be contiguous int64 [B]");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kFloat32 && table.is_contiguous() &&
+                  table.dim() == 2 && table.size(1) == c.hd,
+              "rope_append_q8: table must be fp32 [maxlen, hd]");
+  TORCH_CHECK(c.B * c.H * c.hd < (1LL << 27), "rope_append_q8: shape too large");
+  const at::DeviceGuard g(qkv.device());
+  dpfs_rope_append_q8(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(), table.data_ptr<float>(), k8.data_ptr(),
+                      v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(), len.data_ptr<int>(), rows ? 1 : 0,
+                      (int)c.B, (int)c.H, (int)c.hd, (int)c.Tmax, stream());
+}
+
 // Per-tensor fp8 quantisation with current scaling: (q, inv) with q = sat(x * FMAX / amax)
 // in float8_e4m3fn (fmt 0) or float8_e5m2 (fmt 1), inv = amax / FMAX as an fp32 0-d tensor
 // (the scale torch._scaled_mm multiplies back).  No host synchronisation.
@@ -260,6 +372,14 @@ void bind_decode(py::module_& m) {
         py::arg("n"), py::arg("scale"));
   m.def("_kv_append_chunk", &kv_append_chunk, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("len"),
         py::arg("n") = py::none());
+  m.def("_attn_decode_q8", &attn_decode_q8, py::arg("q"), py::arg("k8"), py::arg("v8"), py::arg("ks"), py::arg("vs"),
+        py::arg("len"), py::arg("scale"));
+  m.def("_attn_extend_q8", &attn_extend_q8, py::arg("q"), py::arg("k8"), py::arg("v8"), py::arg("ks"), py::arg("vs"),
+        py::arg("len"), py::arg("n"), py::arg("scale"));
+  m.def("_kv_append_chunk_q8", &kv_append_chunk_q8, py::arg("qkv"), py::arg("k8"), py::arg("v8"), py::arg("ks"),
+        py::arg("vs"), py::arg("len"), py::arg("n") = py::none());
+  m.def("_rope_append_q8", &rope_append_q8, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k8"),
+        py::arg("v8"), py::arg("ks"), py::arg("vs"), py::arg("len"));
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);

@@ -42,6 +42,10 @@ void dpfs_attn_extend(const void* q, long long ldq, const void* kc, const void* 
                       const int* n, void* o, int B, int T, int H, int HD, int Tmax, float scale, hipStream_t s);
 void dpfs_kv_append_chunk(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc, const int* len,
                           int len_rows, const int* n, int B, int T, int H, int HD, int Tmax, hipStream_t s);
+// fp8 KV cache: e4m3 codes k8 / v8 (B, Tmax, H, HD) with fp32 row scales ks / vs (B, Tmax, H)
+void dpfs_attn_extend_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
+                         const float* vs, const int* len, int len_rows, const int* n, void* o, int B, int T, int H,
+                         int HD, int Tmax, float scale, hipStream_t s);
 
 // kernels/attention_fused.hip
 void dpfs_attn_bwd_dkdv4(int items, const void* q, const void* k, const void* v, const void* dout, const float* lsn,
@@ -77,6 +81,10 @@ void dpfs_kv_append_rows(const void* ksrc, const void* vsrc, long long ld, void*
 void dpfs_rope_append_rows(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kc, void* vc,
                            const int* len, int B, int H, int HD, int Tmax, hipStream_t s);
 void dpfs_step_advance_rows(int* len, int64_t* pos, int B, int t_max, hipStream_t s);
+// fp8 KV cache: e4m3 codes k8 / v8 (B, Tmax, H, HD) with fp32 row scales ks / vs (B, Tmax, H)
+void dpfs_attn_decode_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
+                         const float* vs, const int* len, int len_rows, void* o, long long ldo, float* part, int B,
+                         int H, int HD, int Tmax, float scale, hipStream_t s);
 
 // kernels/elementwise.hip
 void dpfs_swiglu_fwd(int dtype, const void* gu, void* h, int M, int F, int perm, hipStream_t s);
@@ -219,6 +227,13 @@ int dpfs_gemm_tn_group(int n, const void* const* A, const void* const* B, float*
                        const int* lda, const int* ldb, const int* acc, int K, float* ws, long long ws_floats,
                        const void* const* A2, const void* const* B2, const int* lda2, const int* ldb2, int K1,
                        hipStream_t s);
+
+// kernels/kv8.hip
+void dpfs_kv_append_chunk_q8(const void* ksrc, const void* vsrc, long long ld, void* k8, void* v8, float* ks,
+                             float* vs, const int* len, int len_rows, const int* n, int B, int T, int H, int HD,
+                             int Tmax, hipStream_t s);
+void dpfs_rope_append_q8(void* qkv, long long ld, const int64_t* pos, const float* tab, void* k8, void* v8, float* ks,
+                         float* vs, const int* len, int len_rows, int B, int H, int HD, int Tmax, hipStream_t s);
 
 // kernels/norm.hip
 int dpfs_norm_bwd_grid(int M);

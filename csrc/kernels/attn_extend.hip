@@ -26,7 +26,15 @@
 //    LDS region (wave-local ordering only), and at the end the waves' (m, l, O) partials meet
 //    in LDS and are merged in wave order: deterministic, no atomics, no waiting between
 //    workgroups.
+//
+// fp8 KV cache (Q8 = true; the row format is in kv8.h): the cache operands are e4m3 codes with
+// one fp32 scale per (b, key, h) row, converted where they are used and nothing else changed:
+// the K fragment becomes bf16_rn(f32(code) * ks[row]) (one scale per lane per tile: the lane's
+// A-operand row) and the V chunks staged to LDS bf16_rn(f32(code) * vs[row]), so the kernel
+// equals, bit for bit, the bf16 form run on caches dequantised to bf16 by that expression.  The
+// prefetched tile is held as codes (half the registers of the bf16 prefetch).
 #include "common.h"
+#include "kv8.h"
 #include "../dpfs_api.h"
 #include "attn_common.h"
 
@@ -43,9 +51,10 @@ __device__ __forceinline__ int ext_swz(int r, int ch) {
   return HD == 64 ? (ch ^ (((r >> 1) & 1) << 2)) : (ch ^ ((r & 3) << 2));
 }
 
-template <int HD>
+template <int HD, bool Q8 = false>
 __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q, long long ldq,
-                                                     const bf16* __restrict__ kc, const bf16* __restrict__ vc,
+                                                     const void* __restrict__ kcv, const void* __restrict__ vcv,
+                                                     const float* __restrict__ ksc, const float* __restrict__ vsc,
                                                      const int* __restrict__ len_ptr, int len_rows,
                                                      const int* __restrict__ n_ptr, bf16* __restrict__ o, int T,
                                                      int H, int Tmax, float scale) {
@@ -98,8 +107,11 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
   // the last key of this lane's query, relative to its first key row of a tile (4 hf)
   const int qlim = (live ? len + tq : -1) - 4 * hf;
 
-  const bf16* kbase = kc + ((long long)b * Tmax * H + h) * HD;
-  const bf16* vbase = vc + ((long long)b * Tmax * H + h) * HD;
+  const bf16* kbase = (const bf16*)kcv + ((long long)b * Tmax * H + h) * HD;
+  const bf16* vbase = (const bf16*)vcv + ((long long)b * Tmax * H + h) * HD;
+  const uint8_t* k8base = (const uint8_t*)kcv + ((long long)b * Tmax * H + h) * HD;
+  const uint8_t* v8base = (const uint8_t*)vcv + ((long long)b * Tmax * H + h) * HD;
+  const long long sbase = (long long)b * Tmax * H + h;   // scale of key row k: sbase + k * H
   const long long ldkv = (long long)H * HD;
   char* lv = smem + wave * VT;
   // V^T fragment reads (as attn_fwd3_k): rows 16 s + 4 hf + (i16 >> 2) [+ 8], d columns
@@ -112,22 +124,45 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
     voff[dt] = row * RB + (ext_swz<HD>(row, col >> 3) << 4) + (col & 7) * 2;
   }
 
-  bf16x8 kreg[KS];
-  u32x4 vreg[NVC];
+  // the prefetched tile: bf16 values, or with Q8 codes (8 per register pair) and their row scales
+  bf16x8 kreg[Q8 ? 1 : KS];
+  u32x4 vreg[Q8 ? 1 : NVC];
+  u32x2 kreg8[Q8 ? KS : 1], vreg8[Q8 ? NVC : 1];
+  float ksreg = 0.f, vsreg[Q8 ? NVC : 1];
   // K fragment (A operand): lane holds K[k0 + r32][16 ks + 8 hf + j]; rows past kmax are masked
   // after the product, so they may hold anything, but the address stays inside the cache.
   // V rows past kmax are zeros: their P is 0, and 0 x NaN would not be.
   auto fetch = [&](int kt) __attribute__((always_inline)) {
     const int k0 = kt * kExtK;
-    const bf16* krow = kbase + (long long)min(k0 + r32, kmax) * ldkv + 8 * hf;
+    if constexpr (Q8) {
+      const int kr = min(k0 + r32, kmax);
+      const uint8_t* krow = k8base + (long long)kr * ldkv + 8 * hf;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) kreg[ks] = *reinterpret_cast<const bf16x8*>(krow + 16 * ks);
+      for (int ks = 0; ks < KS; ++ks) kreg8[ks] = *reinterpret_cast<const u32x2*>(krow + 16 * ks);
+      ksreg = ksc[sbase + (long long)kr * H];
 #pragma unroll
-    for (int i = 0; i < NVC; ++i) {
-      const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (k0 + r <= kmax) v = *reinterpret_cast<const u32x4*>(vbase + (long long)(k0 + r) * ldkv + ch * 8);
-      vreg[i] = v;
+      for (int i = 0; i < NVC; ++i) {
+        const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
+        u32x2 v = {0u, 0u};
+        float sc = 0.f;                      // rows past kmax: code 0 x scale 0 = the staged zero
+        if (k0 + r <= kmax) {
+          v = *reinterpret_cast<const u32x2*>(v8base + (long long)(k0 + r) * ldkv + ch * 8);
+          sc = vsc[sbase + (long long)(k0 + r) * H];
+        }
+        vreg8[i] = v;
+        vsreg[i] = sc;
+      }
+    } else {
+      const bf16* krow = kbase + (long long)min(k0 + r32, kmax) * ldkv + 8 * hf;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) kreg[ks] = *reinterpret_cast<const bf16x8*>(krow + 16 * ks);
+#pragma unroll
+      for (int i = 0; i < NVC; ++i) {
+        const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (k0 + r <= kmax) v = *reinterpret_cast<const u32x4*>(vbase + (long long)(k0 + r) * ldkv + ch * 8);
+        vreg[i] = v;
+      }
     }
   };
 
@@ -147,11 +182,17 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
 #pragma unroll
     for (int i = 0; i < NVC; ++i) {
       const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
-      *reinterpret_cast<u32x4*>(lv + r * RB + (ext_swz<HD>(r, ch) << 4)) = vreg[i];
+      if constexpr (Q8)
+        *reinterpret_cast<bf16x8*>(lv + r * RB + (ext_swz<HD>(r, ch) << 4)) = kv8_dec8_bf16(vreg8[i], vsreg[i]);
+      else
+        *reinterpret_cast<u32x4*>(lv + r * RB + (ext_swz<HD>(r, ch) << 4)) = vreg[i];
     }
     bf16x8 kcur[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) kcur[ks] = kreg[ks];
+    for (int ks = 0; ks < KS; ++ks) {
+      if constexpr (Q8) kcur[ks] = kv8_dec8_bf16(kreg8[ks], ksreg);
+      else kcur[ks] = kreg[ks];
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     if (kt + 4 < nkt) fetch(kt + 4);   // the next tile's loads fly under this tile's math
@@ -294,9 +335,24 @@ extern "C" void dpfs_attn_extend(const void* q, long long ldq, const void* kc, c
                                  int len_rows, const int* n, void* o, int B, int T, int H, int HD, int Tmax,
                                  float scale, hipStream_t s) {
   const dim3 grid((T + kExtQ - 1) / kExtQ, B * H);
-#define EXT_LAUNCH(HD_)                                                                                         \
-  attn_extend_k<HD_><<<grid, 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, len, len_rows, n, \
+#define EXT_LAUNCH(HD_)                                                                                     \
+  attn_extend_k<HD_><<<grid, 256, 0, s>>>((const bf16*)q, ldq, kc, vc, nullptr, nullptr, len, len_rows, n, \
                                           (bf16*)o, T, H, Tmax, scale)
+  if (HD == 32) EXT_LAUNCH(32);
+  else if (HD == 64) EXT_LAUNCH(64);
+  else EXT_LAUNCH(128);
+#undef EXT_LAUNCH
+}
+
+// The fp8-cache form: k8 / v8 contiguous (B, Tmax, H, HD) e4m3 codes that already hold the
+// chunk's rows (dpfs_kv_append_chunk_q8), ks / vs contiguous (B, Tmax, H) fp32 scales.
+extern "C" void dpfs_attn_extend_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
+                                    const float* vs, const int* len, int len_rows, const int* n, void* o, int B, int T,
+                                    int H, int HD, int Tmax, float scale, hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H);
+#define EXT_LAUNCH(HD_)                                                                                         \
+  attn_extend_k<HD_, true><<<grid, 256, 0, s>>>((const bf16*)q, ldq, k8, v8, ks, vs, len, len_rows, n, (bf16*)o, T, H, \
+                                                Tmax, scale)
   if (HD == 32) EXT_LAUNCH(32);
   else if (HD == 64) EXT_LAUNCH(64);
   else EXT_LAUNCH(128);

@@ -26,18 +26,30 @@
 // uniform kernel computes at *len = L.  step_advance_rows_k clamps every row at the cache
 // capacity: a row that reaches it is frozen (appends nothing, attends inside its cache rows,
 // keeps its position inside the RoPE table) while the shorter rows of the batch go on.
+//
+// fp8 KV cache (Q8 = true; the row format is in kv8.h): kc / vc hold e4m3 codes and ksc / vsc one
+// fp32 scale per (b, key, h) row.  The codes are converted to fp32 where they are loaded; the
+// key's scale multiplies its finished dot product and the value's scale is folded into p in front
+// of the P.V FMAs (the row sum keeps the unscaled p): one multiply per key per side.  Grid,
+// splits, wave merge and partial format are those of the bf16 form.
 #include "common.h"
+#include "kv8.h"
 #include "../dpfs_api.h"
 
 namespace dpfs {
 
 constexpr int kSplit = 256;   // keys per workgroup
 
-template <int HD, bool ROWS>
+template <int HD, bool ROWS, bool Q8 = false>
 __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restrict__ q, long long ldq,
-                                                          const bf16* __restrict__ kc, const bf16* __restrict__ vc,
+                                                          const void* __restrict__ kcv, const void* __restrict__ vcv,
+                                                          const float* __restrict__ ksc, const float* __restrict__ vsc,
                                                           const int* __restrict__ len_ptr, int H, int Tmax,
                                                           float scale, float* __restrict__ part) {
+  const bf16* __restrict__ kc = (const bf16*)kcv;
+  const bf16* __restrict__ vc = (const bf16*)vcv;
+  const uint8_t* __restrict__ k8 = (const uint8_t*)kcv;
+  const uint8_t* __restrict__ v8 = (const uint8_t*)vcv;
   constexpr int NV = HD / 8;               // 16-byte vectors per row
   const int split = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
   KASSERT(!ROWS || len_ptr[b] >= 0, "cache length %d of sequence %d", len_ptr[b], b);
@@ -63,7 +75,23 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
   // scores: lane-per-key
   const int key = k0 + wave * 64 + l;
   float s = -INFINITY;
-  if (key < L) {
+  if (Q8 && key < L) {
+    const long long row = ((long long)b * Tmax + key) * H + h;
+    const uint8_t* krow = k8 + row * HD;
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < HD / 16; ++c) {
+      const u32x4 w = *reinterpret_cast<const u32x4*>(krow + 16 * c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float v[4];
+        kv8_dec4(w[i], v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = fmaf(qf[16 * c + 4 * i + j], v[j], acc);
+      }
+    }
+    s = acc * ksc[row];
+  } else if (key < L) {
     const bf16* krow = kc + (((long long)b * Tmax + key) * H + h) * HD;
     float acc = 0.f;
 #pragma unroll
@@ -94,7 +122,28 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
   for (int i = 0; i < DG; ++i) {
     const int kk = kg + KG * i;             // key within the wave's 64
     const float pk = p_lds[wave][kk];
-    if (kw0 + kk < L) {
+    if (Q8 && kw0 + kk < L) {
+      const long long row = ((long long)b * Tmax + kw0 + kk) * H + h;
+      const uint8_t* vrow = v8 + row * HD + dg * DPL;
+      const float pv = pk * vsc[row];
+      uint32_t w[DPL / 4];
+      if (DPL == 16) {
+        const u32x4 t = *reinterpret_cast<const u32x4*>(vrow);
+#pragma unroll
+        for (int c = 0; c < DPL / 4; ++c) w[c] = t[c];
+      } else {
+        const u32x2 t = *reinterpret_cast<const u32x2*>(vrow);
+        w[0] = t[0];
+        w[1] = t[1];
+      }
+#pragma unroll
+      for (int c = 0; c < DPL / 4; ++c) {
+        float v[4];
+        kv8_dec4(w[c], v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[4 * c + j] = fmaf(pv, v[j], o[4 * c + j]);
+      }
+    } else if (kw0 + kk < L) {
       const bf16* vrow = vc + (((long long)b * Tmax + kw0 + kk) * H + h) * HD + dg * DPL;
 #pragma unroll
       for (int c = 0; c < DPL / 8; ++c) {
@@ -353,8 +402,18 @@ template <int HD, bool ROWS>
 static void launch_attn_decode(const void* q, long long ldq, const void* kc, const void* vc, const int* len_ptr, void* o,
                                long long ldo, float* part, int B, int H, int Tmax, float scale, hipStream_t s) {
   const int ns = dpfs_decode_nsplit(Tmax);
-  attn_decode_split_k<HD, ROWS><<<dim3(ns, B * H), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc,
-                                                                  len_ptr, H, Tmax, scale, part);
+  attn_decode_split_k<HD, ROWS><<<dim3(ns, B * H), 256, 0, s>>>((const bf16*)q, ldq, kc, vc, nullptr, nullptr, len_ptr, H,
+                                                                  Tmax, scale, part);
+  attn_decode_combine_k<HD, ROWS><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
+}
+
+template <int HD, bool ROWS>
+static void launch_attn_decode_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
+                                  const float* vs, const int* len_ptr, void* o, long long ldo, float* part, int B,
+                                  int H, int Tmax, float scale, hipStream_t s) {
+  const int ns = dpfs_decode_nsplit(Tmax);
+  attn_decode_split_k<HD, ROWS, true><<<dim3(ns, B * H), 256, 0, s>>>((const bf16*)q, ldq, k8, v8, ks, vs, len_ptr, H,
+                                                                        Tmax, scale, part);
   attn_decode_combine_k<HD, ROWS><<<B * H, 64, 0, s>>>(part, ns, len_ptr, (bf16*)o, ldo, H);
 }
 
@@ -376,6 +435,24 @@ extern "C" void dpfs_attn_decode_rows(const void* q, long long ldq, const void* 
                                       void* o, long long ldo, float* part, int B, int H, int HD, int Tmax, float scale,
                                       hipStream_t s) {
   attn_decode_hd<true>(q, ldq, kc, vc, len, o, ldo, part, B, H, HD, Tmax, scale, s);
+}
+
+// The fp8-cache form: k8 / v8 contiguous (B, Tmax, H, HD) e4m3 codes, ks / vs contiguous
+// (B, Tmax, H) fp32 scales; len one device int32 (len_rows 0) or B of them (len_rows 1).
+extern "C" void dpfs_attn_decode_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
+                                    const float* vs, const int* len, int len_rows, void* o, long long ldo, float* part,
+                                    int B, int H, int HD, int Tmax, float scale, hipStream_t s) {
+#define DEC_Q8(HD_, ROWS_) launch_attn_decode_q8<HD_, ROWS_>(q, ldq, k8, v8, ks, vs, len, o, ldo, part, B, H, Tmax, scale, s)
+  if (len_rows) {
+    if (HD == 32) DEC_Q8(32, true);
+    else if (HD == 64) DEC_Q8(64, true);
+    else DEC_Q8(128, true);
+  } else {
+    if (HD == 32) DEC_Q8(32, false);
+    else if (HD == 64) DEC_Q8(64, false);
+    else DEC_Q8(128, false);
+  }
+#undef DEC_Q8
 }
 
 extern "C" void dpfs_kv_append(const void* ksrc, const void* vsrc, long long ld, void* kc, void* vc,

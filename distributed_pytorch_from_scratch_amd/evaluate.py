@@ -76,6 +76,8 @@ def get_test_args(argv=None):
                    help="prompts decoded together as one ragged batch (1: one by one, the reference)")
     g.add_argument("--prefill_chunk", type=int, default=0,
                    help="prefill a prompt in pieces of at most this many tokens (0: whole)")
+    g.add_argument("--kv_cache_dtype", choices=["act", "fp8"], default="act",
+                   help="KV cache storage: the activation dtype, or e4m3 codes with per-row fp32 scales")
     g = p.add_argument_group("other")
     g.add_argument("--random_seed", type=int, default=0)
     g.add_argument("--device", type=str, default=None)
@@ -100,14 +102,15 @@ def calc_loss(model: Transformer, dataloader, dev) -> float:
 @torch.inference_mode()
 def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True,
                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                  prefill_chunk: int = 0):
+                  prefill_chunk: int = 0, kv_dtype=None):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
     (``models/generation.py``); ``False`` re-runs the whole prefix per token like the reference.
     ``temperature`` > 0 samples instead (``top_k`` / ``top_p`` / ``seed`` as in ``generate``);
     sampling runs in the KV-cached decode step only.  ``prefill_chunk`` > 0 prefills the prompt
-    in pieces of at most that many tokens (KV-cached decoding only)."""
+    in pieces of at most that many tokens (KV-cached decoding only); ``kv_dtype`` "fp8" keeps the
+    KV cache as e4m3 codes (``generate``)."""
     if temperature != 0 and not kv_cache:
         raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
     if kv_cache:
@@ -115,7 +118,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
         n0 = 1 + len(prompt_ids)
         tokens = torch.tensor([bos] + list(prompt_ids), dtype=torch.long, device=dev).view(1, -1)
         out = generate(model, tokens, max_new_tokens=max(1, max_len + 1 - n0), eos_id=eos, temperature=temperature,
-                       top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk)[0]
+                       top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype)[0]
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
             out = out[:-1]
@@ -135,7 +138,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
 
 @torch.inference_mode()
 def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
-                        top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0):
+                        top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None):
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
@@ -146,14 +149,15 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
         return []
     lens = [1 + len(p) for p in prompts]
     if max(lens) > max_len:   # such a prompt still gets its one token (greedy_decode): one by one
-        return [greedy_decode(model, p, bos, eos, max_len, dev, True, temperature, top_k, top_p, seed, prefill_chunk)
+        return [greedy_decode(model, p, bos, eos, max_len, dev, True, temperature, top_k, top_p, seed, prefill_chunk,
+                              kv_dtype)
                 for p in prompts]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
         tokens[b, :lens[b]] = torch.tensor([bos] + p, dtype=torch.long, device=dev)
     outs = generate(model, tokens, max_new_tokens=max_len + 1 - min(lens), eos_id=eos, max_len=max_len + 1,
                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, prompt_lens=lens,
-                    prefill_chunk=prefill_chunk)
+                    prefill_chunk=prefill_chunk, kv_dtype=kv_dtype)
     res = []
     for p, out in zip(prompts, outs):
         out = out[1:]
@@ -213,6 +217,8 @@ def test(rank, args):
     ds = loader.dataset
     sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.sample_seed,
                     prefill_chunk=args.prefill_chunk)
+    if args.kv_cache_dtype != "act":
+        sampling["kv_dtype"] = args.kv_cache_dtype
     decoded = []
     if args.synthetic_prompts or not args.tokenizer_path:
         prompts = [torch.randint(3, margs.vocab_size, (8,), generator=torch.Generator().manual_seed(i)).tolist()
@@ -247,6 +253,8 @@ def main(argv=None):
         raise ValueError("--decode_batch must be >= 1, and > 1 batches the KV-cached decode step: drop --no_kv_cache")
     if args.prefill_chunk < 0 or (args.prefill_chunk > 0 and args.no_kv_cache):
         raise ValueError("--prefill_chunk must be >= 0, and > 0 chunks the KV-cached prefill: drop --no_kv_cache")
+    if args.kv_cache_dtype != "act" and args.no_kv_cache:
+        raise ValueError("--kv_cache_dtype chooses the storage of the KV cache: drop --no_kv_cache")
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)
     mp.spawn(test, args=(args,), nprocs=args.tp_size, join=True)

@@ -32,6 +32,14 @@ that fills the cache (it is frozen: appends nothing, reads only its cache rows) 
 rows go on.  The lengths are device data like the positions, so one captured graph serves every
 mix of prompt lengths of the same ``(B, t_max)``.
 
+fp8 KV cache (``kv_dtype="fp8"``; the default ``None`` keeps the activation dtype): keys and
+values are stored as OCP e4m3 codes with one fp32 scale per cached (token, head) row
+(``ops/reference.py:_kv_quant_rows`` is the format), ``(hd + 4) / (2 hd)`` of the bf16 cache.  The
+cache is written by quantising appends (``_kv_append_chunk_q8``, ``_rope_append_q8``) and read
+directly by the fp8 forms of the attention kernels (``_attn_decode_q8``, ``_attn_extend_q8``);
+only storage is fp8, the math stays fp32 / bf16.  The whole-prompt prefill attends its own fresh,
+unquantised q / k / v; everything that reads the cache later sees the quantised rows.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -58,10 +66,21 @@ from ..parallel import tp_comm
 
 
 class KVCache:
-    """Per-layer key/value buffers ``(B, T_max, H_local, hd)`` in the activation dtype."""
+    """Per-layer key/value buffers ``(B, T_max, H_local, hd)`` in the activation dtype
+    (``kv_dtype`` None), or with ``kv_dtype="fp8"`` as ``torch.float8_e4m3fn`` codes plus the fp32
+    row scales ``ks`` / ``vs`` ``(B, T_max, H_local)`` (head_dim 32, 64 or 128)."""
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
-                 ragged: bool = False):
+                 ragged: bool = False, kv_dtype: Optional[str] = None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"KVCache: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
+        if kv_dtype == "fp8":
+            if hd not in (32, 64, 128):
+                raise ValueError(f"KVCache: kv_dtype='fp8' needs head_dim 32, 64 or 128, got {hd}")
+            dtype = torch.float8_e4m3fn
+            self.ks = [torch.empty(B, t_max, h_local, dtype=torch.float32, device=device) for _ in range(n_layers)]
+            self.vs = [torch.empty(B, t_max, h_local, dtype=torch.float32, device=device) for _ in range(n_layers)]
         self.k = [torch.empty(B, t_max, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.empty(B, t_max, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
         self.len = 0                      # host view (prefill / multi-token steps); ragged: the longest row
@@ -73,6 +92,17 @@ class KVCache:
     @property
     def ragged(self) -> bool:
         return self.lens is not None
+
+    @property
+    def fp8(self) -> bool:
+        return self.kv_dtype == "fp8"
+
+    def tensors(self):
+        """Every device buffer of the cache (the fp8 form: codes and scales)."""
+        return self.k + self.v + (self.ks + self.vs if self.fp8 else [])
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors())
 
     def reset(self):
         self.len = 0
@@ -109,7 +139,13 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
     """Multi-token step (prefill, or T > 1 continuation) with host-side cache bookkeeping.  The
     continuation (``cache.len > 0``) reads the cache lengths from ``cache.len_t`` (the caller has
     run ``cache.sync_device_len()``); ``n_t`` (device int32 (B,), or None for T) gives the real
-    new tokens of every right-padded row."""
+    new tokens of every right-padded row.
+
+    fp8 cache: the whole-prompt prefill (``cache.len == 0``) still attends the fresh, unquantised
+    q / k / v through ``attn_fwd``; it fills the cache through ``_kv_append_chunk_q8`` at device
+    length 0 (``cache.len_t`` holds 0 there: the caller has synchronised it), the rows the slice
+    copy writes.  A continuation appends and attends through the ``_q8`` kernels, so its queries
+    see the quantised prefix and the quantised rows of their own chunk."""
     attn = layer.attn
     h, hd = attn.num_local_heads, attn.head_dim
     qkv = attn.wqkv(x2d)                                     # (B*T, 3*h*hd)
@@ -121,9 +157,15 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
         q = qkv[:, : h * hd].view(B, T, h, hd)
         kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
         v = qkv[:, 2 * h * hd:].view(B, T, h, hd)
-        cache.k[li][:, :T] = kk
-        cache.v[li][:, :T] = v
+        if cache.fp8:
+            k_._kv_append_chunk_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, None)
+        else:
+            cache.k[li][:, :T] = kk
+            cache.v[li][:, :T] = v
         o, _ = k_.attn_fwd(q, kk, v, scale, True)
+    elif cache.fp8:
+        k_._kv_append_chunk_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t)
+        o = k_._attn_extend_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t, scale)
     else:
         # continuation chunk: every row appends its new keys / values at its own cache length,
         # then its T new queries attend the cached prefix plus the causal part of the chunk
@@ -144,6 +186,8 @@ def _prefill_piece(model, ids: torch.Tensor, cache: KVCache, n: Optional[List[in
     n_t = None
     if cache.len == 0:
         positions = torch.arange(T, device=dev).repeat(B)
+        if cache.fp8:
+            cache.sync_device_len()       # the quantising append of the prefill reads len_t (0)
     else:
         cache.sync_device_len()
         base = cache.lens if cache.ragged else [cache.len] * B
@@ -274,12 +318,17 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
         else:
             x, h1, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, L.s1, L.eps1)
         qkv = proj(h1, W(L.wqkv), L.bqkv)
-        if L.hd % 16 == 0:
-            k.rope_append(qkv, pos, tab, cache.k[li], cache.v[li], cache.len_t)
+        if cache.fp8:   # head_dim 32 / 64 / 128: always the fused kernel
+            k._rope_append_q8(qkv, pos, tab, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t)
+            o = k._attn_decode_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t,
+                                  1.0 / math.sqrt(L.hd))
         else:
-            k.rope_(qkv, pos, tab, 2 * L.h, L.hd, False)
-            k.kv_append(qkv, cache.k[li], cache.v[li], cache.len_t)
-        o = k.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(L.hd))
+            if L.hd % 16 == 0:
+                k.rope_append(qkv, pos, tab, cache.k[li], cache.v[li], cache.len_t)
+            else:
+                k.rope_(qkv, pos, tab, 2 * L.h, L.hd, False)
+                k.kv_append(qkv, cache.k[li], cache.v[li], cache.len_t)
+            o = k.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(L.hd))
         pout = proj(o, W(L.wo))
         tp_comm.all_reduce(pout, async_op=False)
         x, h2, _ = k.add_rmsnorm_fwd(pout, L.bo, x, L.s2, L.eps2)
@@ -313,8 +362,14 @@ def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVC
         qkv = attn.wqkv(layer.norm1(x))                      # (B, 3*h*hd)
         k_ = K(qkv)
         k_.rope_(qkv, pos, tab, 2 * h, hd, False)
-        k_.kv_append(qkv, cache.k[li], cache.v[li], cache.len_t)
-        x = x + attn.wo(k_.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(hd)))
+        if cache.fp8:   # the un-fused single-token append: the chunk kernel at T = 1
+            k_._kv_append_chunk_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, None)
+            o = k_._attn_decode_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t,
+                                   1.0 / math.sqrt(hd))
+        else:
+            k_.kv_append(qkv, cache.k[li], cache.v[li], cache.len_t)
+            o = k_.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(hd))
+        x = x + attn.wo(o)
         x = x + layer.ffn(layer.norm2(x))
     logits = model._lm_head_local(model.norm(x))
     nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
@@ -393,32 +448,36 @@ def _use_graph(dev) -> bool:
             and (p is None or p.tp_size == 1))
 
 
-_SESSIONS = {}   # (id(model), B, t_max, device, ragged) -> KV cache + captured decode graphs
+_SESSIONS = {}   # (id(model), B, t_max, device, kv_dtype, ragged) -> KV cache + captured decode graphs
 
 
-def _session(model, B: int, t_max: int, dev, ragged: bool = False):
-    """The KV cache and decode graphs for this (model, batch, length, uniform / ragged): reused
+def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Optional[str] = None):
+    """The KV cache and decode graphs for this (model, batch, length, cache dtype, uniform /
+    ragged): reused
     by the next generate() call of the same shape, so serving pays the graph capture once (a
     ragged session serves every mix of prompt lengths: they are device data).  Reused only
     while it is the same live model object and no parameter changed since the capture (the
     graphs hold the bf16 weight copies of that version); otherwise rebuilt.  One kept shape
-    per model, and only caches up to DPFS_DECODE_SESSION_MAX_GB (default 16) are kept;
+    per model (with a session per cache dtype of that shape), and only caches up to
+    DPFS_DECODE_SESSION_MAX_GB (default 16; an fp8 cache counts codes and scales) are kept;
     ``clear_sessions()`` frees them."""
     attn0 = model.layers[0].attn
-    key = (id(model), B, t_max, str(dev), ragged)
+    key = (id(model), B, t_max, str(dev), kv_dtype, ragged)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
         ent["cache"].reset()
         return ent["cache"], ent["graphs"]
     cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev,
-                    ragged)
+                    ragged, kv_dtype)
     graphs = {}
-    kv_bytes = sum(t.numel() * t.element_size() for t in cache.k + cache.v)
+    kv_bytes = cache.nbytes()             # the fp8 form: codes and scales
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
     if _use_graph(dev) and kv_bytes <= keep_gb * 2 ** 30:
-        for k in [k for k, e in _SESSIONS.items() if e["model"]() is None or k[0] == id(model)]:
-            del _SESSIONS[k]          # dead models, and other shapes of this one
+        shape = lambda k: k[:4] + k[5:]
+        for k in [k for k, e in _SESSIONS.items()
+                  if e["model"]() is None or (k[0] == id(model) and shape(k) != shape(key))]:
+            del _SESSIONS[k]          # dead models, and other shapes of this one (its other cache dtype stays)
         _SESSIONS[key] = {"model": weakref.ref(model), "vers": vers, "cache": cache, "graphs": graphs}
     return cache, graphs
 
@@ -431,7 +490,8 @@ def clear_sessions():
 @torch.inference_mode()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
              max_len: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-             seed: int = 0, prompt_lens=None, prefill_chunk: int = 0) -> List[List[int]]:
+             seed: int = 0, prompt_lens=None, prefill_chunk: int = 0,
+             kv_dtype: Optional[str] = None) -> List[List[int]]:
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -451,7 +511,13 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
     ``prefill_chunk`` > 0 prefills the prompt in pieces of at most that many tokens
     (``logits_step``): the peak activation memory of the call then scales with the piece, not
-    with T0.  The decode steps, graphs and sessions are the same; 0 prefills the prompt whole."""
+    with T0.  The decode steps, graphs and sessions are the same; 0 prefills the prompt whole.
+
+    ``kv_dtype="fp8"`` keeps the KV cache as e4m3 codes with per-row fp32 scales (about half the
+    bytes; head_dim 32, 64 or 128); ``None`` keeps it in the activation dtype.  A session is kept
+    per cache dtype."""
+    if kv_dtype not in (None, "fp8"):
+        raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
     if prefill_chunk < 0:
         raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
@@ -462,9 +528,9 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     dev = prompt.device
     if prompt_lens is not None:
         return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
-                                sample, prefill_chunk)
+                                sample, prefill_chunk, kv_dtype)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
-    cache, graphs = _session(model, B, t_max, dev)
+    cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype)
     out = [list(map(int, row)) for row in prompt.tolist()]
     done = [False] * B
     if max_new_tokens <= 0 or T0 >= t_max:
@@ -519,7 +585,7 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
 
 def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
-                     prefill_chunk: int = 0):
+                     prefill_chunk: int = 0, kv_dtype: Optional[str] = None):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
     that has filled the cache frozen inside it (``_step_advance_rows``)."""
@@ -527,7 +593,7 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     dev = prompt.device
     cap = min(model.args.maxlen, max_len or model.args.maxlen)     # total length at which a row stops
     t_max = min(cap, max(lens) + max_new_tokens)
-    cache, graphs = _session(model, B, t_max, dev, ragged=True)
+    cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype)
     rows = prompt.tolist()
     out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
     done = [n >= cap for n in lens]

@@ -100,6 +100,11 @@ step_advance = reference.step_advance
 _step_advance_rows = reference._step_advance_rows
 _attn_extend = reference._attn_extend
 _kv_append_chunk = reference._kv_append_chunk
+# the fp8 KV cache ops read bf16 rows on the GPU; an fp32 decode takes the oracle's, like the above
+_kv_append_chunk_q8 = reference._kv_append_chunk_q8
+_rope_append_q8 = reference._rope_append_q8
+_attn_decode_q8 = reference._attn_decode_q8
+_attn_extend_q8 = reference._attn_extend_q8
 gemv_nt = reference.gemv_nt
 
 

@@ -282,6 +282,69 @@ def _attn_extend(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     return o.view(B * T, H * hd).to(q.dtype)
 
 
+# ------------------------------------------------------------------- fp8 KV cache ----
+# Storage: e4m3 codes k8 / v8 (B, T_max, H, hd) torch.float8_e4m3fn and one fp32 scale per cached
+# (token, head) row, ks / vs (B, T_max, H).  The format is the contract of the GPU kernels
+# (csrc/kernels/kv8.h), which produce the same codes and scales bit for bit.
+
+def _kv_quant_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rows ``x[..., hd]`` -> (codes ``[..., hd]`` float8_e4m3fn, inv ``[...]`` fp32):
+    amax = max(max_j |x_j|, 1e-12), scale = 448 / amax, code_j = e4m3fn(clamp(x_j * scale, +-448))
+    (fp32 product, round to nearest even), inv = 1 / scale; the row represents f32(code_j) * inv.
+    fp32 arithmetic, operation for operation that of ``ops/fp8.py`` per row."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1, keepdim=True).clamp_min(1e-12)
+    # tensor / tensor: IEEE fp32 divisions (a Python scalar over a tensor multiplies by the reciprocal)
+    scale = torch.full_like(amax, 448.0) / amax
+    codes = (xf * scale).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return codes, (torch.ones_like(scale) / scale).squeeze(-1)
+
+
+def _kv_dequant(c8: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
+    return c8.float() * cs[..., None]
+
+
+def _kv_append_chunk_q8(qkv: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                        len: torch.Tensor, n: Optional[torch.Tensor] = None) -> None:
+    """The quantising ``_kv_append_chunk``: the k / v parts of packed row b*T + t of qkv
+    [B*T, 3*H*hd] go, as codes and a scale per head, to cache row len[b] + t, for t < n[b] (``n``
+    None: T) and len[b] + t < T_max; every other code and scale is left as it is."""
+    B, Tmax, H, hd = k8.shape
+    T = qkv.size(0) // B
+    rows = qkv.view(B, T, -1)
+    for b, (L, m) in enumerate(_chunk_rows(len, n, B, T, Tmax)):
+        if m > 0:
+            k8[b, L:L + m], ks[b, L:L + m] = _kv_quant_rows(rows[b, :m, H * hd: 2 * H * hd].view(m, H, hd))
+            v8[b, L:L + m], vs[b, L:L + m] = _kv_quant_rows(rows[b, :m, 2 * H * hd: 3 * H * hd].view(m, H, hd))
+
+
+def _rope_append_q8(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor,
+                    ks: torch.Tensor, vs: torch.Tensor, len: torch.Tensor) -> None:
+    """rope_ on the q and k heads of the packed rows [B, 3*H*hd], then the quantising append of the
+    rotated k row and the v row at len / len[b] (a full cache or row appends nothing)."""
+    H, hd = k8.size(2), k8.size(3)
+    rope_(qkv, pos, table, 2 * H, hd, False)
+    _kv_append_chunk_q8(qkv, k8, v8, ks, vs, len)
+
+
+def _attn_decode_q8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                    len: torch.Tensor, scale: float) -> torch.Tensor:
+    """``attn_decode`` over the dequantised caches ``code.float() * inv[..., None]``.  Rows past
+    the attended keys are not read (they may hold NaN codes and scales)."""
+    B, Tmax, H, hd = k8.shape
+    L = min(int(len.max()) + 1, Tmax)
+    kf = torch.zeros(B, Tmax, H, hd, dtype=torch.float32, device=k8.device)
+    vf = torch.zeros_like(kf)
+    kf[:, :L], vf[:, :L] = _kv_dequant(k8[:, :L], ks[:, :L]), _kv_dequant(v8[:, :L], vs[:, :L])
+    return attn_decode(q, kf, vf, len, scale)
+
+
+def _attn_extend_q8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                    len: torch.Tensor, n: Optional[torch.Tensor], scale: float) -> torch.Tensor:
+    """``_attn_extend`` over the dequantised caches ``code.float() * inv[..., None]``."""
+    return _attn_extend(q, _kv_dequant(k8, ks), _kv_dequant(v8, vs), len, n, scale)
+
+
 def gemv_nt_ok(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> bool:
     return True
 

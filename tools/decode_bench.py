@@ -5,6 +5,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
                                  [--temperature T --top_k K --top_p P] [--repeats R] [--sample-kernel]
                                  [--ragged | --ragged-equal]
                                  [--prefill-chunk N [N ...]] [--continuation --t0 1024 --chunk 256]
+                                 [--kv-dtype {act,fp8,both}] [--modes graph eager]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -26,6 +27,11 @@ peak allocation above the cache (``max_memory_allocated``).  ``--continuation`` 
 (``_kv_append_chunk`` + ``_attn_extend``) and on the framework formulation they replaced (slice
 assignment, fp32 einsum / softmax / einsum over the whole cache), in interleaved rounds
 (``--repeats`` of them) with the medians.
+
+``--kv-dtype fp8`` decodes with the fp8 KV cache (``generate(..., kv_dtype="fp8")``); ``both`` runs
+the activation-dtype cache and the fp8 cache in interleaved rounds (``--repeats`` of them, each
+dtype's session warm) and adds one line per (batch, mode, dtype) with the median and the kept
+session's cache bytes.  ``--modes`` restricts the run to the graph or the eager step.
 """
 from __future__ import annotations
 
@@ -57,10 +63,14 @@ def main():
     ap.add_argument("--continuation", action="store_true", help="time one multi-token continuation")
     ap.add_argument("--t0", type=int, default=1024, help="--continuation: ids in the cache")
     ap.add_argument("--chunk", type=int, default=256, help="--continuation: new ids")
+    ap.add_argument("--kv-dtype", choices=["act", "fp8", "both"], default="act",
+                    help="KV cache storage: activation dtype, fp8 codes, or both in interleaved rounds")
+    ap.add_argument("--modes", nargs="+", choices=["graph", "eager"], default=["graph", "eager"])
     a = ap.parse_args()
     sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
     import torch
     from distributed_pytorch_from_scratch_amd.models import get_preset, Transformer
+    from distributed_pytorch_from_scratch_amd.models import generation as G
     from distributed_pytorch_from_scratch_amd.models.generation import generate
     from distributed_pytorch_from_scratch_amd.utils.dist import init_dist_env
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -87,23 +97,37 @@ def main():
         elif a.ragged_equal:
             lens = [a.prompt] * B
         kw = dict(sampling, prompt_lens=lens) if lens else sampling
-        for mode in ("graph", "eager"):
+        kds = {"act": [None], "fp8": ["fp8"], "both": [None, "fp8"]}[a.kv_dtype]
+        for mode in a.modes:
             os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
-            generate(m, prompt, max_new_tokens=a.new, **kw)         # warm-up: GEMM choices, graph capture
-                                                                    #   (reused by the same-shape call)
+            for kd in kds:
+                generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **kw)   # warm-up: GEMM choices, graph
+                                                                                #   capture (reused by the same-shape call)
+            ms = {kd: [] for kd in kds}
             for _ in range(a.repeats):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                generate(m, prompt, max_new_tokens=a.new, **kw)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
-                rec = {"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
-                       "ms_per_step": round(1000 * dt / a.new, 3), "tokens_per_s": round(B * a.new / dt, 1)}
-                if lens:
-                    rec.update(ragged="spread" if a.ragged else "equal", min_len=min(lens), max_len=max(lens))
-                if a.temperature > 0:
-                    rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
-                print(json.dumps(rec), flush=True)
+                for kd in kds:                                      # interleaved rounds
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **kw)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    ms[kd].append(round(1000 * dt / a.new, 3))
+                    rec = {"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
+                           "ms_per_step": round(1000 * dt / a.new, 3), "tokens_per_s": round(B * a.new / dt, 1)}
+                    if a.kv_dtype != "act":
+                        rec["kv_dtype"] = kd or "act"
+                    if lens:
+                        rec.update(ragged="spread" if a.ragged else "equal", min_len=min(lens), max_len=max(lens))
+                    if a.temperature > 0:
+                        rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+                    print(json.dumps(rec), flush=True)
+            if a.kv_dtype != "act":
+                kept = {k[4]: e["cache"].nbytes() for k, e in G._SESSIONS.items()}
+                for kd in kds:
+                    print(json.dumps({"bench": "kv_dtype", "model": a.model, "batch": B, "mode": mode, "prompt": a.prompt,
+                                      "new": a.new, "kv_dtype": kd or "act", "ms_per_step": ms[kd],
+                                      "ms_per_step_median": _median(ms[kd]), "session_cache_bytes": kept.get(kd)}),
+                          flush=True)
         if a.ragged and B > 1:
             # the same prompts one after the other at batch 1 (uniform path, graph), each timed
             # right after its own warm-up call, so no capture is in the time
