@@ -554,9 +554,9 @@ def gemm_tn_group(k, items) -> list:
     outs = [it[2] for it in items]
 
     def each(dsts):
-        if two:
-            return [gemm_tn_pair(k, a, b, a1, b1, d, acc) for (a, b, _, acc, a1, b1), d in zip(items, dsts)]
-        return [gemm_tn(k, a, b, d, acc) for (a, b, _, acc, _, _), d in zip(items, dsts)]
+        # (per item: a group that mixes one- and two-buffer items runs each in its own form)
+        return [gemm_tn_pair(k, a, b, a1, b1, d, acc) if a1 is not None else gemm_tn(k, a, b, d, acc)
+                for (a, b, _, acc, a1, b1), d in zip(items, dsts)]
 
     if (not TN_GROUP or _direct(k) or len(items) < 2 or any(o is None for o in outs) or not items[0][0].is_cuda
             or not hasattr(k, "gemm_tn_group") or mode() not in ("auto", "ours")

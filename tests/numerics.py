@@ -90,10 +90,12 @@ def worst_ratio(out, ref64, unit):
     return float(flat[i]), i, ratio
 
 
-def assert_within(out, ref64, unit, limit, what, tiles=None):
+def assert_within(out, ref64, unit, limit, what, tiles=None, where=None):
     """max(err / unit) <= limit over every element (unit == 0 demands err == 0).  ``tiles`` maps a
     dimension to the kernel's tile sizes along it, e.g. {0: (256, 128, 16), 1: (256, 192)}: the
     failure message gives the worst element's index modulo each, so an edge fault names itself.
+    ``where``: a callable from the worst element's index to a string appended to the failure
+    message (tests/numerics_items.py: the persistent GEMM's item, workgroup and round).
     Returns the worst ratio."""
     assert out.shape == ref64.shape == unit.shape, (what, out.shape, ref64.shape, unit.shape)
     worst, i, ratio = worst_ratio(out, ref64, unit)
@@ -113,7 +115,8 @@ def assert_within(out, ref64, unit, limit, what, tiles=None):
     raise AssertionError(
         f"{what}: worst err/unit {worst:.4g} > {limit:.4g} at {idx}"
         f" (out {float(out[idx]):.8g}, ref {float(ref64[idx]):.8g}, unit {float(unit[idx]):.3g})"
-        + (f" [{mods}]" if mods else "") + f"; {n_over} of {ratio.numel()} elements over the limit")
+        + (f" [{mods}]" if mods else "") + (f" [{where(idx)}]" if where is not None else "")
+        + f"; {n_over} of {ratio.numel()} elements over the limit")
 
 
 def bias_stat(out, ref64, acc_term, what, max_drop=0.10):

@@ -114,3 +114,19 @@ def test_adam_oracle_matches_torch():
         opt.step()
         R.adam_step([p], [g], [m], [v], None, 1e-2, 0.9, 0.99, 1e-8, 0.1, step)
     assert torch.allclose(p, ref.detach(), atol=1e-6)
+
+
+def test_gemm_tn_group_runs_each_item_in_its_own_form_on_the_oracle():
+    """The selector's per-item fallback: a group that mixes one- and two-buffer items gives every
+    item its own sum, whichever form comes first (a first one-buffer item used to drop the later
+    items' second buffers, a first two-buffer item to fail on the one-buffer ones)."""
+    from distributed_pytorch_from_scratch_amd.ops import gemm_select as GS
+    g = torch.Generator().manual_seed(7)
+    a, b, a1, b1 = (torch.randn(12, n, generator=g) for n in (8, 16, 8, 16))
+    one, two = a.t() @ b, a.t() @ b + a1.t() @ b1
+    for order in ((False, True), (True, False)):
+        outs = [torch.full((8, 16), float("nan")) for _ in order]
+        items = [(a, b, o, False) + ((a1, b1) if second else ()) for second, o in zip(order, outs)]
+        r = GS.gemm_tn_group(R, items)
+        for second, o, x in zip(order, outs, r):
+            assert x is o and torch.allclose(o, two if second else one, atol=1e-5)
