@@ -327,37 +327,99 @@ void step_advance_rows(torch::Tensor len, torch::Tensor pos, int64_t t_max) {
 }
 
 // Temperature / top-k / top-p sampling of one token per row (kernels/sample.hip): logits
-// [B, >= vocab] bf16 / fp32 with unit column stride, columns >= vocab are padding.  top_k 0 or
-// >= vocab and top_p 1 are off.  The uniform of row b is Philox4x32-10(key seed, counter
-// (pos[b], b, 0)) unless `u` [B] supplies it (tests).  Returns (ids int64, kept int32, thresh
-// fp32, u fp32), each [B].  No host synchronisation: graph-capturable.
+// [B, >= vocab] bf16 / fp32 with unit column stride, columns >= vocab are padding.  What the
+// scalar and the per-row launch share, in two steps so that the scalar call checks its arguments
+// in the order it always has: the logits / vocab checks, then the pos / u checks and the outputs.
+struct SampleCall {
+  int dt;
+  int64_t B, ld;
+  bool vec_ok;
+  const float* u;
+  torch::Tensor ids, kept, thresh, uo;
+};
+
+SampleCall sample_rows(const torch::Tensor& logits, int64_t vocab, const char* op) {
+  check_rowmajor(logits, "logits");
+  SampleCall c;
+  c.dt = dcode(logits);
+  c.B = logits.size(0);
+  c.ld = logits.stride(0);
+  const int64_t vec = c.dt == 1 ? 8 : 4;
+  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab < (1LL << 31) && (c.B <= 1 || c.ld >= logits.size(1)), op,
+              ": 1 <= vocab <= ld, got vocab ", vocab, " for rows of ", logits.size(1));
+  // 16-byte row loads need aligned rows whose last vector lies inside the row
+  const int64_t esz = c.dt == 1 ? 2 : 4;
+  c.vec_ok = reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 && (c.B <= 1 || c.ld * esz % 16 == 0) &&
+             (vocab + vec - 1) / vec * vec <= logits.size(1);
+  return c;
+}
+
+// (the caller holds a DeviceGuard of the logits' device)
+void sample_outputs(SampleCall& c, const torch::Tensor& pos, const c10::optional<torch::Tensor>& u, const char* op) {
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == c.B, op,
+              ": pos must be contiguous int64 [B]");
+  c.u = opt_f32(u, c.B, "u");
+  c.ids = torch::empty({c.B}, pos.options());
+  c.kept = torch::empty({c.B}, pos.options().dtype(torch::kInt32));
+  c.thresh = torch::empty({c.B}, pos.options().dtype(torch::kFloat32));
+  c.uo = torch::empty({c.B}, pos.options().dtype(torch::kFloat32));
+}
+
+// One (temperature, top_k, top_p, seed) for every row.  top_k 0 or >= vocab and top_p 1 are
+// off.  The uniform of row b is Philox4x32-10(key seed, counter (pos[b], b, 0)) unless `u` [B]
+// supplies it (tests).  Returns (ids int64, kept int32, thresh fp32, u fp32), each [B].  No host
+// synchronisation: graph-capturable.
 py::tuple sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
                         int64_t seed, torch::Tensor pos, c10::optional<torch::Tensor> u) {
-  check_rowmajor(logits, "logits");
-  const int dt = dcode(logits);
-  const int64_t B = logits.size(0), ld = logits.stride(0), vec = dt == 1 ? 8 : 4;
-  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab < (1LL << 31) && (B <= 1 || ld >= logits.size(1)),
-              "sample_logits: 1 <= vocab <= ld, got vocab ", vocab, " for rows of ", logits.size(1));
+  SampleCall c = sample_rows(logits, vocab, "sample_logits");
   TORCH_CHECK(temperature > 0.0, "sample_logits: temperature must be > 0, got ", temperature);
   TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
   TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0, got ", top_k);
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == B,
-              "sample_logits: pos must be contiguous int64 [B]");
-  const float* up = opt_f32(u, B, "u");
   const at::DeviceGuard g(logits.device());
-  auto ids = torch::empty({B}, pos.options());
-  auto kept = torch::empty({B}, pos.options().dtype(torch::kInt32));
-  auto thresh = torch::empty({B}, pos.options().dtype(torch::kFloat32));
-  auto uo = torch::empty({B}, pos.options().dtype(torch::kFloat32));
-  // 16-byte row loads need aligned rows whose last vector lies inside the row
-  const int64_t esz = dt == 1 ? 2 : 4;
-  const bool vec_ok = reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 && (B <= 1 || ld * esz % 16 == 0) &&
-                      (vocab + vec - 1) / vec * vec <= logits.size(1);
+  sample_outputs(c, pos, u, "sample_logits");
   const int k = (int)std::min<int64_t>(top_k, vocab);
-  dpfs_sample_logits(logits.data_ptr(), dt, ld, (int)B, (int)vocab, vec_ok ? 1 : 0, (float)(1.0 / temperature), k, top_p,
-                     (unsigned long long)seed, pos.data_ptr<int64_t>(), up, ids.data_ptr<int64_t>(),
-                     kept.data_ptr<int>(), thresh.data_ptr<float>(), uo.data_ptr<float>(), stream());
-  return py::make_tuple(ids, kept, thresh, uo);
+  dpfs_sample_logits(logits.data_ptr(), c.dt, c.ld, (int)c.B, (int)vocab, c.vec_ok ? 1 : 0,
+                     (float)(1.0 / temperature), k, top_p, (unsigned long long)seed, pos.data_ptr<int64_t>(), c.u,
+                     c.ids.data_ptr<int64_t>(), c.kept.data_ptr<int>(), c.thresh.data_ptr<float>(),
+                     c.uo.data_ptr<float>(), stream());
+  return py::make_tuple(c.ids, c.kept, c.thresh, c.uo);
+}
+
+// One setting of a per-row launch: B values of `type` in the logits' device memory.
+const void* row_setting(const torch::Tensor& t, at::ScalarType type, const torch::Tensor& logits, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == logits.device() && t.scalar_type() == type && t.dim() == 1 &&
+                  t.is_contiguous() && t.numel() == logits.size(0),
+              "sample_logits_rows: ", name, " must be a contiguous ", type, " tensor of B = ", logits.size(0),
+              " elements on the device of logits, got ", t.sizes(), " of ", t.scalar_type(), " on ", t.device());
+  return t.data_ptr();
+}
+
+// sample_logits with the settings of every row in device memory: inv_t fp32 = fp32(1 / T), 0
+// marks a greedy row (ids = the first maximum, kept = the number of maxima, thresh = the
+// maximum, u = 0); top_k int32, <= 0 or >= vocab is off; top_p fp64, >= 1 is off; seed int64, the
+// Philox key; rid int32, the counter word where the scalar form puts the row index.  The device
+// values are not read here (their range is the caller's to check where the lists come from): no
+// host synchronisation, graph-capturable, and one captured launch serves every setting.  Bound as
+// _sample_logits_rows: tests/golden/ext_api.txt, which records the public names, cannot change
+// with this function, so its signature and docstring are recorded in
+// tests/golden/ext_api_sample_rows.txt instead (tests/test_ext_api_sample_rows.py).
+py::tuple sample_logits_rows(torch::Tensor logits, int64_t vocab, torch::Tensor inv_t, torch::Tensor top_k,
+                             torch::Tensor top_p, torch::Tensor seed, torch::Tensor rid, torch::Tensor pos,
+                             c10::optional<torch::Tensor> u) {
+  SampleCall c = sample_rows(logits, vocab, "sample_logits_rows");
+  const at::DeviceGuard g(logits.device());
+  sample_outputs(c, pos, u, "sample_logits_rows");
+  TORCH_CHECK(pos.device() == logits.device() && (c.u == nullptr || u->device() == logits.device()),
+              "sample_logits_rows: pos and u must be on the device of logits");
+  const auto* it = static_cast<const float*>(row_setting(inv_t, torch::kFloat32, logits, "inv_t"));
+  const auto* tk = static_cast<const int*>(row_setting(top_k, torch::kInt32, logits, "top_k"));
+  const auto* tp = static_cast<const double*>(row_setting(top_p, torch::kFloat64, logits, "top_p"));
+  const auto* sd = static_cast<const int64_t*>(row_setting(seed, torch::kInt64, logits, "seed"));
+  const auto* ri = static_cast<const int*>(row_setting(rid, torch::kInt32, logits, "rid"));
+  dpfs_sample_logits_rows(logits.data_ptr(), c.dt, c.ld, (int)c.B, (int)vocab, c.vec_ok ? 1 : 0, it, tk, tp, sd, ri,
+                          pos.data_ptr<int64_t>(), c.u, c.ids.data_ptr<int64_t>(), c.kept.data_ptr<int>(),
+                          c.thresh.data_ptr<float>(), c.uo.data_ptr<float>(), stream());
+  return py::make_tuple(c.ids, c.kept, c.thresh, c.uo);
 }
 
 }  // namespace
@@ -387,4 +449,6 @@ void bind_decode(py::module_& m) {
         py::arg("v_cache"), py::arg("len"));
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),
         py::arg("top_p"), py::arg("seed"), py::arg("pos"), py::arg("u") = py::none());
+  m.def("_sample_logits_rows", &sample_logits_rows, py::arg("logits"), py::arg("vocab"), py::arg("inv_t"),
+        py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("rid"), py::arg("pos"), py::arg("u") = py::none());
 }

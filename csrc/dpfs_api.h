@@ -252,6 +252,10 @@ void dpfs_norm_bwd(int mode, int dtype, const void* dy, const void* x, const flo
 void dpfs_sample_logits(const void* logits, int dtype, long long ld, int B, int vocab, int vec_ok, float inv_t,
                         int top_k, double top_p, unsigned long long seed, const int64_t* pos, const float* u_in,
                         int64_t* ids, int* kept, float* thresh, float* u_out, hipStream_t s);
+void dpfs_sample_logits_rows(const void* logits, int dtype, long long ld, int B, int vocab, int vec_ok,
+                             const float* inv_t, const int* top_k, const double* top_p, const int64_t* seed,
+                             const int* rid, const int64_t* pos, const float* u_in, int64_t* ids, int* kept,
+                             float* thresh, float* u_out, hipStream_t s);
 
 // comm/rccl_comm.hip
 const char* dpfs_rccl_last_error();

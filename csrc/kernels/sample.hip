@@ -12,6 +12,16 @@
 //           (seed lo, seed hi) and counter (pos lo, pos hi, row, 0) -- a pure function of
 //           (seed, row, position), so eager steps, graph replays and every TP rank agree.
 //
+// Per-row settings (ROWS = true): workgroup b reads (1/T, top_k, top_p, seed, row id) from five
+// device arrays instead of the launch arguments, so a batch mixes requests and a captured
+// launch serves every setting; the row id takes the place of b in the Philox counter (a request
+// keyed on (seed, position) alone draws the same in any slot).  1/T == 0 marks a greedy row:
+// no radix select, the threshold is the row maximum and u = 0, so the draw below returns the
+// smallest index of the maximum (every maximum weighs 2^40).  The settings are uniform within
+// the workgroup: control flow stays wave-uniform.  Any array content is safe: the values only
+// steer comparisons and arithmetic, every loop is bounded by the row, and ids[b] is preset to 0
+// (settings out of range, which the host rejects, may leave no crossing to write it).
+//
 // Selection never sorts: a logit's raw bits map to an order-preserving integer key (the order
 // is unchanged by the positive scale 1/T) and both thresholds are found by an 8-bit radix
 // descent over that key, most significant digit first (2 rounds for bf16, 4 for fp32) --
@@ -139,7 +149,12 @@ struct Shared {
 // Radix descent for the largest key t with  (count | mass){key >= t} >= target, over the
 // elements with key >= floor_key.  MASS = false: counts, target = k.  MASS = true: 2^40
 // fixed-point masses, target = ceil(p * their total).  Every thread of the block calls it.
-template <typename T, bool MASS>
+// ROWS is not used in the body; it only names the calling kernel.  Keep it: with it every
+// instantiation has one caller, and the uniform kernel compiles to the instructions it had
+// before the per-row kernel existed.  Shared between the two kernels, the function is inlined
+// with other register and scheduling choices, and the uniform kernel's code changes silently
+// (diff the disassembly of sample_logits_k<T, false> against the previous build to check).
+template <typename T, bool MASS, bool ROWS>
 __device__ uint32_t radix_select(const Row<T>& row, Shared& sh, uint32_t floor_key, u64 k_target, double p,
                                  float inv_t, float zmax) {
   constexpr int BITS = KeyBits<T>::BITS, ND = BITS / 8;
@@ -225,16 +240,33 @@ __device__ __forceinline__ uint32_t philox4x32_10_x0(uint32_t c0, uint32_t c1, u
   return c0;
 }
 
-template <typename T>
+// ROWS = false: the settings are the launch arguments inv_t .. seed and the *_r arrays are not
+// read (trailing arguments, so the uniform kernel's code is what it was without them).
+// ROWS = true: workgroup b takes them from inv_t_r[b] .. rid_r[b].
+template <typename T, bool ROWS>
 __global__ __launch_bounds__(1024) void sample_logits_k(const T* __restrict__ logits, long long ld, int vocab,
                                                         bool vec_ok, float inv_t, int top_k, double top_p,
                                                         u64 seed, const int64_t* __restrict__ pos,
                                                         const float* __restrict__ u_in, int64_t* __restrict__ ids,
                                                         int* __restrict__ kept, float* __restrict__ thresh,
-                                                        float* __restrict__ u_out) {
+                                                        float* __restrict__ u_out, const float* __restrict__ inv_t_r,
+                                                        const int* __restrict__ top_k_r,
+                                                        const double* __restrict__ top_p_r,
+                                                        const int64_t* __restrict__ seed_r,
+                                                        const int* __restrict__ rid_r) {
   constexpr int N = Vec<T>::N;
   __shared__ Shared sh;
   const int b = blockIdx.x, nw = blockDim.x >> 6;
+  uint32_t rid = (uint32_t)b;
+  if constexpr (ROWS) {
+    inv_t = inv_t_r[b];
+    top_k = top_k_r[b];
+    top_p = top_p_r[b];
+    seed = (u64)seed_r[b];
+    rid = (uint32_t)rid_r[b];
+    if (threadIdx.x == 0) ids[b] = 0;   // ordered before the draw's store by the barriers below
+  }
+  const bool greedy = ROWS && inv_t == 0.f;
   Row<T> row;
   row.p = logits + (long long)b * ld;
   row.vocab = vocab;
@@ -267,8 +299,12 @@ __global__ __launch_bounds__(1024) void sample_logits_k(const T* __restrict__ lo
   const float zmax = key_to_float<T>(kmax) * inv_t;
 
   uint32_t thr = kmin;
-  if (top_k > 0 && top_k < vocab) thr = radix_select<T, false>(row, sh, 0u, (u64)top_k, 1.0, inv_t, zmax);
-  if (top_p < 1.0) thr = radix_select<T, true>(row, sh, thr, 0, top_p, inv_t, zmax);
+  if (greedy) {
+    thr = kmax;
+  } else {
+    if (top_k > 0 && top_k < vocab) thr = radix_select<T, false, ROWS>(row, sh, 0u, (u64)top_k, 1.0, inv_t, zmax);
+    if (top_p < 1.0) thr = radix_select<T, true, ROWS>(row, sh, thr, 0, top_p, inv_t, zmax);
+  }
 
   // kept mass and count per wave, in index order
   u64 tot = 0;
@@ -299,11 +335,13 @@ __global__ __launch_bounds__(1024) void sample_logits_k(const T* __restrict__ lo
   }
 
   float u;
-  if (u_in != nullptr) {
+  if (greedy) {
+    u = 0.f;   // need = 1: the first index of the maximum
+  } else if (u_in != nullptr) {
     u = u_in[b];
   } else {
     const u64 ps = (u64)pos[b];
-    const uint32_t x0 = philox4x32_10_x0((uint32_t)ps, (uint32_t)(ps >> 32), (uint32_t)b, 0u, (uint32_t)seed,
+    const uint32_t x0 = philox4x32_10_x0((uint32_t)ps, (uint32_t)(ps >> 32), rid, 0u, (uint32_t)seed,
                                          (uint32_t)(seed >> 32));
     u = (float)(x0 >> 8) * 5.9604644775390625e-8f;   // 2^-24
   }
@@ -364,6 +402,14 @@ __global__ __launch_bounds__(1024) void sample_logits_k(const T* __restrict__ lo
 
 using namespace dpfs;
 
+// threads of a workgroup: one per 16-byte vector of the row, whole waves, at most 16 of them
+static int sample_threads(int dtype, int vocab) {
+  const int n = dtype == kBF16 ? 8 : 4;
+  const int nv = (vocab + n - 1) / n;
+  const int nt = (nv + 63) & ~63;
+  return nt < 64 ? 64 : (nt > 64 * kSampleMaxWaves ? 64 * kSampleMaxWaves : nt);
+}
+
 // logits [B, >= vocab] (dtype kBF16 / kF32, unit column stride, row stride ld elements);
 // vec_ok: rows are 16-byte aligned and padded to whole 16-byte vectors past vocab.
 extern "C" void dpfs_sample_logits(const void* logits, int dtype, long long ld, int B, int vocab, int vec_ok,
@@ -371,15 +417,32 @@ extern "C" void dpfs_sample_logits(const void* logits, int dtype, long long ld, 
                                    const float* u_in, int64_t* ids, int* kept, float* thresh, float* u_out,
                                    hipStream_t s) {
   if (B <= 0) return;
-  const int n = dtype == kBF16 ? 8 : 4;
-  const int nv = (vocab + n - 1) / n;
-  int nt = (nv + 63) & ~63;
-  nt = nt < 64 ? 64 : (nt > 64 * kSampleMaxWaves ? 64 * kSampleMaxWaves : nt);
+  const int nt = sample_threads(dtype, vocab);
   if (dtype == kBF16)
-    sample_logits_k<bf16><<<B, nt, 0, s>>>((const bf16*)logits, ld, vocab, vec_ok != 0, inv_t, top_k, top_p, seed, pos,
-                                           u_in, ids, kept, thresh, u_out);
+    sample_logits_k<bf16, false><<<B, nt, 0, s>>>((const bf16*)logits, ld, vocab, vec_ok != 0, inv_t, top_k, top_p,
+                                                  seed, pos, u_in, ids, kept, thresh, u_out, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr);
   else
-    sample_logits_k<float><<<B, nt, 0, s>>>((const float*)logits, ld, vocab, vec_ok != 0, inv_t, top_k, top_p, seed,
-                                            pos, u_in, ids, kept, thresh, u_out);
+    sample_logits_k<float, false><<<B, nt, 0, s>>>((const float*)logits, ld, vocab, vec_ok != 0, inv_t, top_k, top_p,
+                                                   seed, pos, u_in, ids, kept, thresh, u_out, nullptr, nullptr,
+                                                   nullptr, nullptr, nullptr);
+  LAUNCH_CHECK();
+}
+
+// The per-row form: inv_t (fp32; 0 marks a greedy row), top_k (int32; <= 0 or >= vocab: off),
+// top_p (fp64; >= 1: off), seed (int64, the Philox key) and rid (int32, counter word 2) hold
+// B values each in device memory.
+extern "C" void dpfs_sample_logits_rows(const void* logits, int dtype, long long ld, int B, int vocab, int vec_ok,
+                                        const float* inv_t, const int* top_k, const double* top_p,
+                                        const int64_t* seed, const int* rid, const int64_t* pos, const float* u_in,
+                                        int64_t* ids, int* kept, float* thresh, float* u_out, hipStream_t s) {
+  if (B <= 0) return;
+  const int nt = sample_threads(dtype, vocab);
+  if (dtype == kBF16)   // (the scalar settings are not read)
+    sample_logits_k<bf16, true><<<B, nt, 0, s>>>((const bf16*)logits, ld, vocab, vec_ok != 0, 0.f, 0, 1.0, 0ull, pos,
+                                                 u_in, ids, kept, thresh, u_out, inv_t, top_k, top_p, seed, rid);
+  else
+    sample_logits_k<float, true><<<B, nt, 0, s>>>((const float*)logits, ld, vocab, vec_ok != 0, 0.f, 0, 1.0, 0ull, pos,
+                                                  u_in, ids, kept, thresh, u_out, inv_t, top_k, top_p, seed, rid);
   LAUNCH_CHECK();
 }

@@ -11,7 +11,9 @@ Fixed reference bugs: the decode loads ``ckpt_paths[-1]`` (the
 indexes the last *character* of a path string, ``test.py:124``), and the embedding no longer
 mutates the token buffer, so TP>1 decoding is correct.  Extensions: ``--synthetic_prompts``
 (token-id prompts when no tokenizer file is available), the vocab-parallel loss, and sampled
-decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily), and
+decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily;
+``--per_prompt_seed`` gives prompt i the seed ``sample_seed + i`` and a stream of its own, the
+same one by one and in any batch), and
 ``--decode_batch N``: the prompts are decoded N at a time as one ragged batch (per-row KV
 lengths, ``models/generation.py``) instead of one by one.
 """
@@ -72,6 +74,8 @@ def get_test_args(argv=None):
     g.add_argument("--top_k", type=int, default=0, help="sample from the k largest logits (0: off)")
     g.add_argument("--top_p", type=float, default=1.0, help="sample from the top-p nucleus (1: off)")
     g.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling draws")
+    g.add_argument("--per_prompt_seed", action="store_true",
+                   help="prompt i samples with seed sample_seed + i, whatever batch row decodes it")
     g.add_argument("--decode_batch", type=int, default=1,
                    help="prompts decoded together as one ragged batch (1: one by one, the reference)")
     g.add_argument("--prefill_chunk", type=int, default=0,
@@ -107,11 +111,12 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
     (``models/generation.py``); ``False`` re-runs the whole prefix per token like the reference.
-    ``temperature`` > 0 samples instead (``top_k`` / ``top_p`` / ``seed`` as in ``generate``);
+    ``temperature`` > 0 samples instead (``top_k`` / ``top_p`` / ``seed`` as in ``generate``, a
+    one-element sequence for the per-row form: ``seed=[s]`` draws with (s, position) alone);
     sampling runs in the KV-cached decode step only.  ``prefill_chunk`` > 0 prefills the prompt
     in pieces of at most that many tokens (KV-cached decoding only); ``kv_dtype`` "fp8" keeps the
     KV cache as e4m3 codes (``generate``)."""
-    if temperature != 0 and not kv_cache:
+    if not kv_cache and (temperature != 0 or isinstance(seed, (list, tuple, torch.Tensor))):
         raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
     if kv_cache:
         from .models.generation import generate
@@ -142,16 +147,20 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
-    (``seed``, b, position)."""
+    (``seed``, b, position).  Each of ``temperature``, ``top_k``, ``top_p`` and ``seed`` may be a
+    sequence with one value per prompt (``generate``): with a seed per prompt, row b draws with
+    (``seed[b]``, position) alone."""
     from .models.generation import generate
     prompts = [list(p) for p in prompts]
     if not prompts:
         return []
     lens = [1 + len(p) for p in prompts]
     if max(lens) > max_len:   # such a prompt still gets its one token (greedy_decode): one by one
-        return [greedy_decode(model, p, bos, eos, max_len, dev, True, temperature, top_k, top_p, seed, prefill_chunk,
-                              kv_dtype)
-                for p in prompts]
+        seq = lambda v: isinstance(v, (list, tuple, torch.Tensor))
+        row = lambda v, b: [v[b]] if seq(v) else v                # a prompt's own value, still per row
+        return [greedy_decode(model, p, bos, eos, max_len, dev, True, row(temperature, b), row(top_k, b),
+                              row(top_p, b), row(seed, b), prefill_chunk, kv_dtype)
+                for b, p in enumerate(prompts)]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
         tokens[b, :lens[b]] = torch.tensor([bos] + p, dtype=torch.long, device=dev)
@@ -170,12 +179,17 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
 def _decode_all(model, prompts, ds, args, dev, sampling):
     """Continuations of ``prompts`` (lists of ids): one by one, or ``--decode_batch`` at a time."""
     n = args.decode_batch
+    # --per_prompt_seed: prompt i draws with (sample_seed + i, position), one by one and in a batch
+    seeds = lambda i, m: {"seed": [sampling["seed"] + j for j in range(i, i + m)]} if args.per_prompt_seed else {}
     if n <= 1:
-        return [greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache, **sampling)
-                for ids in prompts]
+        return [greedy_decode(model, ids, ds.bos, ds.eos, args.max_decode_len, dev, not args.no_kv_cache,
+                              **{**sampling, **seeds(i, 1)})
+                for i, ids in enumerate(prompts)]
     outs = []
     for i in range(0, len(prompts), n):
-        outs += greedy_decode_batch(model, prompts[i:i + n], ds.bos, ds.eos, args.max_decode_len, dev, **sampling)
+        part = prompts[i:i + n]
+        outs += greedy_decode_batch(model, part, ds.bos, ds.eos, args.max_decode_len, dev,
+                                    **{**sampling, **seeds(i, len(part))})
     return outs
 
 
@@ -247,8 +261,9 @@ def test(rank, args):
 
 def main(argv=None):
     args = get_test_args(argv)
-    if args.no_kv_cache and args.temperature != 0:
-        raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
+    if args.no_kv_cache and (args.temperature != 0 or args.per_prompt_seed):
+        raise ValueError("sampling (--temperature > 0, --per_prompt_seed) runs in the KV-cached decode step: drop "
+                         "--no_kv_cache")
     if args.decode_batch < 1 or (args.decode_batch > 1 and args.no_kv_cache):
         raise ValueError("--decode_batch must be >= 1, and > 1 batches the KV-cached decode step: drop --no_kv_cache")
     if args.prefill_chunk < 0 or (args.prefill_chunk > 0 and args.no_kv_cache):

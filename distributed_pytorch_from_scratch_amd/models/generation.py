@@ -22,7 +22,11 @@ for the local head shard:
 
 The token choice is ``argmax`` (greedy, the default) or, with ``temperature > 0``, one
 ``sample_logits`` launch (csrc/kernels/sample.hip: temperature, top-k, top-p, a stateless
-Philox draw keyed on (seed, row, position)) inside the same captured step.
+Philox draw keyed on (seed, row, position)) inside the same captured step.  The four settings
+may also be given per row (sequences of B values): the rows of a batch then mix greedy and
+sampled requests of any settings, the values live in a device table of the session
+(``SampleRows``) that the captured ``_sample_logits_rows`` launches read, and a call with new
+settings or seeds is a copy into that table, never a new capture.
 
 Ragged batches (``generate(..., prompt_lens=...)``): the prompts of a batch may differ in
 length.  The prompt is right-padded; ``cache.len_t`` then holds one int32 per sequence and the
@@ -55,7 +59,8 @@ import torch
 # decode steps captured per HIP graph replay (the host reads the tokens / checks EOS once per
 # replay; profiles/r2_decode_bench.jsonl)
 _GRAPH_STEPS = 8
-# captured graphs kept per session (greedy: 2; sampling: 2 per (temperature, top_k, top_p, seed))
+# captured graphs kept per session (greedy: 2; sampling: 2 per (temperature, top_k, top_p, seed);
+# per-row sampling: 2 for every setting)
 _MAX_GRAPHS = 16
 
 from ..ops import gemm_select as GS
@@ -88,6 +93,7 @@ class KVCache:
         self.len_t = torch.zeros(B if ragged else 1, dtype=torch.int32, device=device)
         self.lens = [0] * B if ragged else None   # host view of the per-row lengths
         self.t_max = t_max
+        self._sample_rows = None          # the per-row sampling settings (device), made on first use
 
     @property
     def ragged(self) -> bool:
@@ -103,6 +109,13 @@ class KVCache:
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def sample_rows(self) -> "SampleRows":
+        """The cache's table of per-row sampling settings: like ``len_t`` it is device state of
+        the batch that the captured steps read, one per session."""
+        if self._sample_rows is None:
+            self._sample_rows = SampleRows(self.k[0].size(0), self.len_t.device)
+        return self._sample_rows
 
     def reset(self):
         self.len = 0
@@ -133,6 +146,69 @@ class KVCache:
         if self.ragged:
             return self.len_t.clamp(max=self.t_max - 1).long()
         return self.len_t.long().expand(B).contiguous()
+
+
+class SampleRows:
+    """The sampling settings of every row of a batch as device data, (B,) each, in the layout
+    ``_sample_logits_rows`` reads: ``inv_t`` fp32 = fp32(1 / temperature) with 0 for a greedy row,
+    ``top_k`` int32, ``top_p`` fp64, ``seed`` int64 and the Philox row id ``rid`` int32."""
+
+    def __init__(self, B: int, device):
+        dts = (torch.float32, torch.int32, torch.float64, torch.int64, torch.int32)
+        self.inv_t, self.top_k, self.top_p, self.seed, self.rid = (torch.zeros(B, dtype=dt, device=device)
+                                                                   for dt in dts)
+
+    def tensors(self):
+        return self.inv_t, self.top_k, self.top_p, self.seed, self.rid
+
+    def load(self, host) -> "SampleRows":
+        """Copy the five host lists of ``_row_settings`` into the table."""
+        for t, v in zip(self.tensors(), host):
+            t.copy_(torch.tensor(v, dtype=t.dtype))
+        return self
+
+
+def _row_settings(B: int, temperature, top_k, top_p, seed):
+    """The per-row form of the sampling settings: None when all four are scalars (one setting
+    for the batch), else the five host lists of a ``SampleRows`` table, every scalar broadcast
+    to the B rows and every value checked by the rules of the scalar call.  With one ``seed``
+    for the batch row b keeps the row id b, so equal settings given as lists draw what the
+    scalar call draws; with a seed per row the row id is 0 and a request's stream depends on
+    (its seed, position) alone, not on its slot."""
+    vals = [temperature, top_k, top_p, seed]
+    seq = [isinstance(v, (list, tuple, torch.Tensor)) for v in vals]
+    if not any(seq):
+        return None
+    names = ("temperature", "top_k", "top_p", "seed")
+    for i, name in enumerate(names):
+        if seq[i]:
+            vals[i] = vals[i].tolist() if isinstance(vals[i], torch.Tensor) else list(vals[i])
+            if len(vals[i]) != B:
+                raise ValueError(f"generate: {name} needs one value per sequence ({B}), got {len(vals[i])}")
+        else:
+            vals[i] = [vals[i]] * B
+    temps, ks, ps, seeds = vals
+    if not (all(t >= 0 for t in temps) and all(k >= 0 for k in ks) and all(0 < p <= 1 for p in ps)):
+        raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1 in every row, got "
+                         f"{temps}, {ks}, {ps}")
+    if not all(-2 ** 63 <= int(sd) < 2 ** 63 for sd in seeds):
+        raise ValueError(f"generate: every seed must fit 64 bits, got {seeds}")
+    inv_t = [1.0 / float(t) if t > 0 else 0.0 for t in temps]      # rounded to fp32 by the table
+    # the table marks a greedy row by fp32(1 / T) == 0: a sampled row must not round to it (or to inf)
+    scale = torch.tensor(inv_t, dtype=torch.float64).float()
+    if any(t > 0 and (s == 0.0 or s == float("inf")) for t, s in zip(temps, scale.tolist())):
+        raise ValueError("generate: a temperature > 0 needs a finite, non-zero fp32(1 / temperature) (0 marks a "
+                         f"greedy row), got {temps}")
+    return (inv_t, [min(int(k), 2 ** 31 - 1) for k in ks], [float(p) for p in ps], [int(sd) for sd in seeds],
+            [0] * B if seq[3] else list(range(B)))
+
+
+def _draw(logits: torch.Tensor, vocab: int, sample, pos: torch.Tensor) -> torch.Tensor:
+    """Ids (B,) sampled from ``logits`` with ``sample`` = (temperature, top_k, top_p, seed), one
+    ``sample_logits`` launch, or a ``SampleRows`` table, one ``_sample_logits_rows`` launch."""
+    if isinstance(sample, SampleRows):
+        return K(logits)._sample_logits_rows(logits, vocab, *sample.tensors(), pos)[0]
+    return K(logits).sample_logits(logits, vocab, *sample, pos)[0]
 
 
 def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int, T: int, n_t=None):
@@ -273,12 +349,13 @@ def _pick(model, logits: torch.Tensor, pos: torch.Tensor, sample):
     """Next ids (B,) and the fp32 (B, vocab) logits from the gathered (B, padded vocab) logits:
     ``argmax`` without ``sample``, else one ``sample_logits`` launch on the gathered rows with
     ``sample`` = (temperature, top_k, top_p, seed) and the step's device positions (every TP
-    rank holds the same rows, seed and positions, so the ranks agree)."""
+    rank holds the same rows, seed and positions, so the ranks agree), or one
+    ``_sample_logits_rows`` launch with ``sample`` a ``SampleRows`` table (every rank fills its
+    table from the same host lists)."""
     if sample is None:
         logits = logits[..., : model.vocab_size].float()
         return logits.argmax(-1), logits
-    temperature, top_k, top_p, seed = sample
-    nxt = K(logits).sample_logits(logits, model.vocab_size, temperature, top_k, top_p, seed, pos)[0]
+    nxt = _draw(logits, model.vocab_size, sample, pos)
     return nxt, logits[..., : model.vocab_size].float()
 
 
@@ -287,8 +364,9 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     cache; advances ``cache.len_t`` and ``pos`` on the device (a ragged cache: per row, clamped
     at the cache capacity).  Returns (next ids (B,),
     logits (B, vocab) fp32); the ids are the ``argmax``, or with ``sample`` = (temperature,
-    top_k, top_p, seed) a draw keyed on (seed, row, ``pos``).  Touches no host state:
-    graph-capturable."""
+    top_k, top_p, seed) a draw keyed on (seed, row, ``pos``), or with a ``SampleRows`` table every
+    row's own choice: ``argmax``, or a draw keyed on (its seed, its row id, ``pos``).  Touches no
+    host state: graph-capturable."""
     from .engine_common import _Layer
     if model.args.norm != "rmsnorm":
         return _decode_step_modules(model, ids, pos, cache, sample)
@@ -384,7 +462,9 @@ class DecodeGraph:
     (that round trip, ~90 us, was idle GPU time in every step).  ``sample`` = (temperature,
     top_k, top_p, seed) captures sampling steps: the settings are launch arguments of the
     captured ``sample_logits`` nodes (a session keys its graphs on them), and the draw reads the
-    device positions, so a replay at any position draws what the eager step draws there."""
+    device positions, so a replay at any position draws what the eager step draws there.
+    ``sample`` = a ``SampleRows`` table captures ``_sample_logits_rows`` nodes that read the
+    settings from the table at replay: one graph for every setting written there later."""
 
     def __init__(self, model, cache: KVCache, B: int, nsteps: int = 1, sample=None):
         dev = cache.len_t.device
@@ -482,6 +562,15 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     return cache, graphs
 
 
+def _session_sample(cache: KVCache, sample):
+    """``sample`` as the decode steps take it, and what names it in a session's graph keys: the
+    scalar settings (or None, greedy) themselves; per-row host lists (``_row_settings``) are
+    copied into the cache's table and the key is "rows" whatever they hold."""
+    if sample is None or isinstance(sample[0], float):
+        return sample, sample
+    return cache.sample_rows().load(sample), "rows"
+
+
 def clear_sessions():
     """Drop every kept KV cache and decode graph (frees their device memory)."""
     _SESSIONS.clear()
@@ -489,8 +578,8 @@ def clear_sessions():
 
 @torch.inference_mode()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
-             max_len: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-             seed: int = 0, prompt_lens=None, prefill_chunk: int = 0,
+             max_len: Optional[int] = None, temperature=0.0, top_k=0, top_p=1.0,
+             seed=0, prompt_lens=None, prefill_chunk: int = 0,
              kv_dtype: Optional[str] = None) -> List[List[int]]:
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
@@ -509,6 +598,18 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     for the token that follows position t of row b depends only on (``seed``, b, t), so the same
     call returns the same tokens on the graph and the eager path and on every TP rank.
 
+    Each of ``temperature``, ``top_k``, ``top_p`` and ``seed`` may also be a sequence of B values
+    (a list, a tuple or a tensor), one per row; if any is, the call runs per row (scalars are
+    broadcast, every value is checked by the same rules, a wrong length is a ``ValueError``).  Row
+    b then decodes greedily where ``temperature[b]`` is 0 and samples with its own settings
+    elsewhere (the table marks a greedy row by fp32(1 / temperature) == 0, so a positive
+    temperature whose fp32 reciprocal is 0 or infinite, above about 1e45 or below about 3e-39,
+    is a ``ValueError`` in this mode).  With a scalar ``seed`` the draw of row b is keyed on (``seed``, b, t) as above, so
+    equal settings given as lists return what the scalar call returns; with a sequence the draw
+    is keyed on (``seed[b]``, 0, t) alone: a request keeps its stream in whatever row of whatever
+    batch it is decoded.  The settings are device data of the session (``SampleRows``): its two
+    per-row graphs are captured once and serve every later setting and seed.
+
     ``prefill_chunk`` > 0 prefills the prompt in pieces of at most that many tokens
     (``logits_step``): the peak activation memory of the call then scales with the piece, not
     with T0.  The decode steps, graphs and sessions are the same; 0 prefills the prompt whole.
@@ -520,12 +621,14 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
     if prefill_chunk < 0:
         raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
-    if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
-        raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
-                         f"{temperature}, {top_k}, {top_p}")
-    sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
     B, T0 = prompt.shape
     dev = prompt.device
+    sample = _row_settings(B, temperature, top_k, top_p, seed)     # host lists; a session's table below
+    if sample is None:
+        if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
+            raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
+                             f"{temperature}, {top_k}, {top_p}")
+        sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
     if prompt_lens is not None:
         return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
                                 sample, prefill_chunk, kv_dtype)
@@ -535,12 +638,13 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     done = [False] * B
     if max_new_tokens <= 0 or T0 >= t_max:
         return out
+    sample, skey = _session_sample(cache, sample)
     logits = logits_step(model, prompt, cache, prefill_chunk=prefill_chunk)
     if sample is None:
         nxt = logits.argmax(-1)
     else:   # the first token follows position T0 - 1
         pos0 = torch.full((B,), T0 - 1, dtype=torch.int64, device=dev)
-        nxt = K(logits).sample_logits(logits, model.vocab_size, *sample, pos0)[0]
+        nxt = _draw(logits, model.vocab_size, sample, pos0)
     cache.sync_device_len()
     pos = torch.full((B,), cache.len, dtype=torch.int64, device=dev)
     chunk = _GRAPH_STEPS
@@ -562,11 +666,11 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         if _use_graph(dev):
             # S steps per replay while S more tokens are wanted and the cache has room for them
             S = chunk if (max_new_tokens - n_gen >= chunk and cache.len + chunk <= t_max) else 1
-            gkey = S if sample is None else (S, sample)
+            gkey = S if sample is None else (S, skey)
             g = graphs.get(gkey)
             if g is None:
                 if sample is not None and len(graphs) >= _MAX_GRAPHS:
-                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != sample]:
+                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != skey]:
                         del graphs[k]     # sampling graphs of earlier settings; greedy ones stay
                 g = graphs[gkey] = DecodeGraph(model, cache, B, S, sample)
             g.pos.fill_(cache.len)
@@ -599,6 +703,7 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     done = [n >= cap for n in lens]
     if max_new_tokens <= 0 or all(done):
         return out
+    sample, skey = _session_sample(cache, sample)
     # The padded prompt up to the longest row that fits the cache; a row at or past the cache
     # capacity is done already and enters the cache full (frozen).
     T = min(max(lens), t_max)
@@ -608,7 +713,7 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
         nxt = logits.argmax(-1)
     else:   # the first token of row b follows position lens[b] - 1
         pos0 = torch.tensor(cache.lens, dtype=torch.int64, device=dev) - 1
-        nxt = K(logits).sample_logits(logits, model.vocab_size, *sample, pos0)[0]
+        nxt = _draw(logits, model.vocab_size, sample, pos0)
     cache.sync_device_len()
     pos = cache.device_pos()
     chunk = _GRAPH_STEPS
@@ -632,11 +737,11 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
             # for them (a finished row may run past its end: the kernels keep it in bounds)
             longest = max(n for n, d in zip(cache.lens, done) if not d)
             S = chunk if (max_new_tokens - n_gen >= chunk and longest + chunk <= t_max) else 1
-            gkey = S if sample is None else (S, sample)
+            gkey = S if sample is None else (S, skey)
             g = graphs.get(gkey)
             if g is None:
                 if sample is not None and len(graphs) >= _MAX_GRAPHS:
-                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != sample]:
+                    for k in [k for k in graphs if isinstance(k, tuple) and k[1] != skey]:
                         del graphs[k]     # sampling graphs of earlier settings; greedy ones stay
                 g = graphs[gkey] = DecodeGraph(model, cache, B, S, sample)
             g.pos.copy_(cache.device_pos())

@@ -427,9 +427,19 @@ def sample_logits(logits: torch.Tensor, vocab: int, temperature: float, top_k: i
     unless ``u`` (B,) supplies it.  Returns (ids int64, kept int32, thresh fp32 -- the final
     cutoff as a raw logit, the row minimum with both filters off --, u fp32), each (B,)."""
     assert temperature > 0 and 0 < top_p <= 1 and top_k >= 0 and 1 <= vocab <= logits.size(1)
+    dev = logits.device
+    if u is None:
+        u = torch.tensor([sample_uniform(seed, p, b) for b, p in enumerate(pos.tolist())], dtype=torch.float32,
+                         device=dev)
+    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32, device=dev)
+    return _sample_with(logits, vocab, inv_t, top_k, top_p, u)
+
+
+def _sample_with(logits: torch.Tensor, vocab: int, inv_t: torch.Tensor, top_k: int, top_p: float, u: torch.Tensor):
+    """``sample_logits`` from the fp32 scale ``inv_t`` = fp32(1 / temperature) (0-d) and the
+    uniforms ``u`` (B,): what the scalar and the per-row oracle share."""
     B, dev = logits.size(0), logits.device
     x = logits[:, :vocab].float()
-    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32, device=dev)
     z = (x * inv_t).double()
     w = torch.exp(z - z.max(-1, keepdim=True).values)
     thresh = x.min(-1).values
@@ -449,9 +459,6 @@ def sample_logits(logits: torch.Tensor, vocab: int, temperature: float, top_k: i
         first = ok.to(torch.int8).argmax(-1, keepdim=True)      # descending order: the largest value
         thresh = xs.gather(-1, first)[:, 0]
         keep = keep & (x >= thresh[:, None])
-    if u is None:
-        u = torch.tensor([sample_uniform(seed, p, b) for b, p in enumerate(pos.tolist())], dtype=torch.float32,
-                         device=dev)
     u = u.to(device=dev, dtype=torch.float32)
     wk = w * keep
     C = wk.cumsum(-1)
@@ -462,6 +469,44 @@ def sample_logits(logits: torch.Tensor, vocab: int, temperature: float, top_k: i
     fallback = torch.where(wk > 0, idx, torch.zeros_like(idx)).max(-1).values
     ids = torch.where(hit.any(-1), ids, fallback)
     return ids, keep.sum(-1).to(torch.int32), thresh, u
+
+
+def sample_logits_rows(logits: torch.Tensor, vocab: int, inv_t: torch.Tensor, top_k: torch.Tensor,
+                       top_p: torch.Tensor, seed: torch.Tensor, rid: torch.Tensor, pos: torch.Tensor,
+                       u: Optional[torch.Tensor] = None):
+    """``sample_logits`` with the settings of every row as data, (B,) each: ``inv_t`` fp32 =
+    fp32(1 / temperature), 0 marks a greedy row; ``top_k`` int32, <= 0 or >= vocab is off;
+    ``top_p`` fp64, >= 1 is off; ``seed`` int64; ``rid`` int32, the row word of the Philox counter
+    (what the scalar form fills with b).  A sampled row b is ``sample_logits`` of
+    ``logits[b:b+1]`` with that row's scalars and u = ``sample_uniform(seed[b], pos[b], rid[b])``
+    unless ``u`` (B,) supplies it.  A greedy row gives the first maximum of its valid columns
+    (``argmax``), kept = the number of maxima, thresh = the maximum and u = 0.  Returns
+    (ids int64, kept int32, thresh fp32, u fp32), each (B,)."""
+    B, dev = logits.size(0), logits.device
+    assert 1 <= vocab <= logits.size(1)
+    for t, dt in ((inv_t, torch.float32), (top_k, torch.int32), (top_p, torch.float64), (seed, torch.int64),
+                  (rid, torch.int32)):
+        assert t.dtype == dt and t.shape == (B,), "one setting per row, in the dtype of its array"
+    ids = torch.empty(B, dtype=torch.int64, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    thresh = torch.empty(B, dtype=torch.float32, device=dev)
+    uo = torch.empty(B, dtype=torch.float32, device=dev)
+    rows = zip(inv_t.tolist(), top_k.tolist(), top_p.tolist(), seed.tolist(), rid.tolist(), pos.tolist())
+    for b, (it, k, p, s, r, ps) in enumerate(rows):
+        if it == 0.0:
+            x = logits[b, :vocab].float()
+            out = x.argmax(), (x == x.max()).sum(), x.max(), 0.0
+        else:
+            ub = torch.tensor([sample_uniform(s, ps, r)], dtype=torch.float32) if u is None else u[b:b + 1]
+            out = (t[0] for t in _sample_with(logits[b:b + 1], vocab, inv_t[b], k if 0 < k < vocab else 0,
+                                              min(p, 1.0), ub))
+        ids[b], kept[b], thresh[b], uo[b] = out
+    return ids, kept, thresh, uo
+
+
+# the name the kernel sets share (the native module binds the per-row form with a leading
+# underscore: its recorded public surface is left as it is)
+_sample_logits_rows = sample_logits_rows
 
 
 def _rot_bthd(x: torch.Tensor, positions: torch.Tensor, table: torch.Tensor, inverse: bool) -> torch.Tensor:

@@ -3,6 +3,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
 
     python tools/decode_bench.py [--model gpt2-small] [--batch 1 8] [--prompt 128] [--new 256]
                                  [--temperature T --top_k K --top_p P] [--repeats R] [--sample-kernel]
+                                 [--per-row] [--seeds {fixed,fresh}]
                                  [--ragged | --ragged-equal]
                                  [--prefill-chunk N [N ...]] [--continuation --t0 1024 --chunk 256]
                                  [--kv-dtype {act,fp8,both}] [--modes graph eager]
@@ -12,6 +13,12 @@ tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the samplin
 (``sample_logits`` in place of ``argmax``; the full-recompute baseline is then skipped);
 ``--repeats`` times each (batch, mode) that many times; ``--sample-kernel`` times the
 ``sample_logits`` launch alone on bf16 rows of the model's padded vocabulary.
+
+``--per-row`` gives the same settings as per-row lists (``generate`` with sequences: the settings
+are device data, one captured graph pair serves them all) with a fresh seed list on every call;
+``--seeds fixed`` keeps one seed list, and ``--seeds fresh`` without ``--per-row`` gives the scalar
+path a new seed on every call, which recaptures its graphs each time.  ``--sample-kernel
+--per-row`` times the ``_sample_logits_rows`` launch alone.
 
 ``--ragged`` decodes a ragged batch (``generate(..., prompt_lens=...)``, the per-row decode
 kernels): the prompt lengths of a batch are spread evenly over [prompt/4, prompt] (row b of B:
@@ -57,6 +64,9 @@ def main():
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--sample-kernel", action="store_true", help="time the sample_logits launch alone")
+    ap.add_argument("--per-row", action="store_true", help="the settings as per-row lists (device table)")
+    ap.add_argument("--seeds", choices=["fixed", "fresh"], default=None,
+                    help="one seed for every call, or a new one per call (default: fresh with --per-row, else fixed)")
     ap.add_argument("--ragged", action="store_true", help="ragged batch: lengths spread over [prompt/4, prompt]")
     ap.add_argument("--ragged-equal", action="store_true", help="per-row path with all lengths = prompt")
     ap.add_argument("--prefill-chunk", type=int, nargs="+", default=None, help="time the prefill whole and in pieces")
@@ -68,6 +78,17 @@ def main():
     ap.add_argument("--modes", nargs="+", choices=["graph", "eager"], default=["graph", "eager"])
     a = ap.parse_args()
     sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
+    fresh = (a.seeds or ("fresh" if a.per_row else "fixed")) == "fresh"
+    calls = [0]
+
+    def settings(B):
+        """The sampling arguments of the next generate() call at batch B."""
+        calls[0] += 1
+        n = calls[0] if fresh else 0
+        if not a.per_row:
+            return dict(sampling, seed=n)
+        return dict(temperature=[a.temperature] * B, top_k=[a.top_k] * B, top_p=[a.top_p] * B,
+                    seed=[n * B + b for b in range(B)])
     import torch
     from distributed_pytorch_from_scratch_amd.models import get_preset, Transformer
     from distributed_pytorch_from_scratch_amd.models import generation as G
@@ -96,19 +117,20 @@ def main():
             lens = [lo + b * (a.prompt - lo) // max(1, B - 1) for b in range(B)] if B > 1 else [a.prompt]
         elif a.ragged_equal:
             lens = [a.prompt] * B
-        kw = dict(sampling, prompt_lens=lens) if lens else sampling
+        kw = dict(prompt_lens=lens) if lens else {}
         kds = {"act": [None], "fp8": ["fp8"], "both": [None, "fp8"]}[a.kv_dtype]
         for mode in a.modes:
             os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
             for kd in kds:
-                generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **kw)   # warm-up: GEMM choices, graph
-                                                                                #   capture (reused by the same-shape call)
+                # warm-up: GEMM choices, graph capture (reused by the same-shape call)
+                generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **settings(B), **kw)
             ms = {kd: [] for kd in kds}
             for _ in range(a.repeats):
                 for kd in kds:                                      # interleaved rounds
+                    st = settings(B)
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **kw)
+                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **st, **kw)
                     torch.cuda.synchronize()
                     dt = time.perf_counter() - t0
                     ms[kd].append(round(1000 * dt / a.new, 3))
@@ -118,8 +140,9 @@ def main():
                         rec["kv_dtype"] = kd or "act"
                     if lens:
                         rec.update(ragged="spread" if a.ragged else "equal", min_len=min(lens), max_len=max(lens))
-                    if a.temperature > 0:
-                        rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+                    if a.temperature > 0 or a.per_row:
+                        rec.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
+                                   settings="per-row" if a.per_row else "scalar", seeds="fresh" if fresh else "fixed")
                     print(json.dumps(rec), flush=True)
             if a.kv_dtype != "act":
                 kept = {k[4]: e["cache"].nbytes() for k, e in G._SESSIONS.items()}
@@ -146,7 +169,7 @@ def main():
                                   "ragged": "spread", "min_len": min(lens), "max_len": max(lens),
                                   "ms_per_step": round(1000 * dt / (B * a.new), 3),
                                   "tokens_per_s": round(B * a.new / dt, 1)}), flush=True)
-        if a.temperature > 0 or lens:
+        if a.temperature > 0 or a.per_row or lens:
             continue
         # reference formulation: every token re-runs the whole prefix (no cache)
         seq = prompt
@@ -278,7 +301,8 @@ def continuation_bench(a, m):
 
 
 def sample_kernel_bench(a, ld: int, vocab: int):
-    """us per ``sample_logits`` launch (device events over 200 launches) on (B, ld) bf16 rows."""
+    """us per ``sample_logits`` launch (``--per-row``: ``_sample_logits_rows`` with the same
+    settings in every row of its table) on (B, ld) bf16 rows: device events over 200 launches."""
     import torch
     from distributed_pytorch_from_scratch_amd.ops import _ext
     C = _ext.require()
@@ -286,17 +310,25 @@ def sample_kernel_bench(a, ld: int, vocab: int):
     for B in a.batch:
         x = (torch.randn(B, ld, device="cuda") * 4).bfloat16()
         pos = torch.zeros(B, dtype=torch.int64, device="cuda")
+        if a.per_row:
+            tab = (torch.full((B,), 1.0 / T, dtype=torch.float64).float().cuda(),
+                   torch.full((B,), a.top_k, dtype=torch.int32, device="cuda"),
+                   torch.full((B,), a.top_p, dtype=torch.float64, device="cuda"),
+                   torch.zeros(B, dtype=torch.int64, device="cuda"), torch.arange(B, dtype=torch.int32, device="cuda"))
+            launch = lambda: C._sample_logits_rows(x, vocab, *tab, pos)
+        else:
+            launch = lambda: C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
         # 200 launches in one graph: the replay is not paced by the host's launch rate
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(3):
-                C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
+                launch()
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for _ in range(200):
-                C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
+                launch()
         g.replay()
         for _ in range(a.repeats):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -304,8 +336,9 @@ def sample_kernel_bench(a, ld: int, vocab: int):
             g.replay()
             e1.record()
             torch.cuda.synchronize()
-            print(json.dumps({"kernel": "sample_logits", "batch": B, "vocab": vocab, "ld": ld, "temperature": T,
-                              "top_k": a.top_k, "top_p": a.top_p, "us_per_call": round(5 * e0.elapsed_time(e1), 2)}),
+            print(json.dumps({"kernel": "sample_logits_rows" if a.per_row else "sample_logits", "batch": B,
+                              "vocab": vocab, "ld": ld, "temperature": T, "top_k": a.top_k, "top_p": a.top_p,
+                              "us_per_call": round(5 * e0.elapsed_time(e1), 2)}),
                   flush=True)
 
 
