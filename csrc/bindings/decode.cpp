@@ -422,6 +422,67 @@ py::tuple sample_logits_rows(torch::Tensor logits, int64_t vocab, torch::Tensor 
   return py::make_tuple(c.ids, c.kept, c.thresh, c.uo);
 }
 
+// One setting of the penalised launch: as row_setting, under that launch's name.
+const void* pen_setting(const torch::Tensor& t, at::ScalarType type, const torch::Tensor& logits, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == logits.device() && t.scalar_type() == type && t.dim() == 1 &&
+                  t.is_contiguous() && t.numel() == logits.size(0),
+              "sample_logits_pen: ", name, " must be a contiguous ", type, " tensor of B = ", logits.size(0),
+              " elements on the device of logits, got ", t.sizes(), " of ", t.scalar_type(), " on ", t.device());
+  return t.data_ptr();
+}
+
+// _sample_logits_rows on penalised logits, with the token history of every row as device state
+// and two log-probabilities per row (ops/reference.py:sample_logits_pen is the contract).  rep,
+// inv_rep = fp32(1 / rep), pres, freq: fp32 [B].  hist: int32 [B, >= vocab], unit column stride;
+// bit 31 of hist[b, i] says that id i occurs in row b's prompt, bits 0..30 count c, the times this
+// launch has drawn i for the row.  Column i of row b is sampled as
+//   x = fp32(logit); if hist != 0: x = x > 0 ? x * inv_rep : x * rep; x = x - freq * fp32(c);
+//   if c > 0: x = x - pres
+// (every operation rounded to fp32), and kept / thresh are in units of x.  With update the launch
+// then adds 1 to hist[b, ids[b]] in place.  Returns (ids int64 [B], kept int32 [B], thresh fp32 [B],
+// u fp32 [B], logp fp32 [B, 2]): logp[b, 0] is the log-probability of ids[b] under the softmax of
+// the raw logits (temperature 1, no penalty, no filter), logp[b, 1] under the distribution the
+// draw used (-log(number of maxima) on a greedy row).  The device values are not read here: no
+// host synchronisation, graph-capturable.  Recorded in tests/golden/ext_api_sample_pen.txt
+// (tests/test_ext_api_sample_pen.py).
+py::tuple sample_logits_pen(torch::Tensor logits, int64_t vocab, torch::Tensor inv_t, torch::Tensor top_k,
+                            torch::Tensor top_p, torch::Tensor seed, torch::Tensor rid, torch::Tensor rep,
+                            torch::Tensor inv_rep, torch::Tensor pres, torch::Tensor freq, torch::Tensor hist,
+                            torch::Tensor pos, c10::optional<torch::Tensor> u, bool update) {
+  SampleCall c = sample_rows(logits, vocab, "sample_logits_pen");
+  const at::DeviceGuard g(logits.device());
+  sample_outputs(c, pos, u, "sample_logits_pen");
+  TORCH_CHECK(pos.device() == logits.device() && (c.u == nullptr || u->device() == logits.device()),
+              "sample_logits_pen: pos and u must be on the device of logits");
+  const auto* it = static_cast<const float*>(pen_setting(inv_t, torch::kFloat32, logits, "inv_t"));
+  const auto* tk = static_cast<const int*>(pen_setting(top_k, torch::kInt32, logits, "top_k"));
+  const auto* tp = static_cast<const double*>(pen_setting(top_p, torch::kFloat64, logits, "top_p"));
+  const auto* sd = static_cast<const int64_t*>(pen_setting(seed, torch::kInt64, logits, "seed"));
+  const auto* ri = static_cast<const int*>(pen_setting(rid, torch::kInt32, logits, "rid"));
+  const auto* rp = static_cast<const float*>(pen_setting(rep, torch::kFloat32, logits, "rep"));
+  const auto* ir = static_cast<const float*>(pen_setting(inv_rep, torch::kFloat32, logits, "inv_rep"));
+  const auto* pr = static_cast<const float*>(pen_setting(pres, torch::kFloat32, logits, "pres"));
+  const auto* fr = static_cast<const float*>(pen_setting(freq, torch::kFloat32, logits, "freq"));
+  TORCH_CHECK(hist.is_cuda() && hist.device() == logits.device() && hist.scalar_type() == torch::kInt32 &&
+                  hist.dim() == 2 && hist.size(0) == c.B && hist.stride(1) == 1,
+              "sample_logits_pen: hist must be an int32 [B = ", c.B, ", >= vocab] tensor with unit column stride on "
+              "the device of logits, got ", hist.sizes(), " of ", hist.scalar_type(), " on ", hist.device());
+  const int64_t ld_h = hist.stride(0);
+  TORCH_CHECK(hist.size(1) >= vocab && (c.B <= 1 || ld_h >= hist.size(1)),
+              "sample_logits_pen: hist needs vocab = ", vocab, " <= columns <= row stride, got rows of ", hist.size(1),
+              " with stride ", ld_h);
+  // 16-byte history loads: aligned rows that hold the last vector of the logits' layout
+  const int64_t vec = c.dt == 1 ? 8 : 4;
+  const bool hvec_ok = reinterpret_cast<uintptr_t>(hist.data_ptr()) % 16 == 0 && (c.B <= 1 || ld_h % 4 == 0) &&
+                       (vocab + vec - 1) / vec * vec <= hist.size(1);
+  auto logp = torch::empty({c.B, 2}, c.thresh.options());
+  dpfs_sample_logits_pen(logits.data_ptr(), c.dt, c.ld, (int)c.B, (int)vocab, c.vec_ok ? 1 : 0, it, tk, tp, sd, ri, rp,
+                         ir, pr, fr, hist.data_ptr<int>(), ld_h, hvec_ok ? 1 : 0, update ? 1 : 0,
+                         pos.data_ptr<int64_t>(), c.u, c.ids.data_ptr<int64_t>(), c.kept.data_ptr<int>(),
+                         c.thresh.data_ptr<float>(), c.uo.data_ptr<float>(), logp.data_ptr<float>(), stream());
+  return py::make_tuple(c.ids, c.kept, c.thresh, c.uo, logp);
+}
+
 }  // namespace
 
 void bind_decode(py::module_& m) {
@@ -451,4 +512,8 @@ void bind_decode(py::module_& m) {
         py::arg("top_p"), py::arg("seed"), py::arg("pos"), py::arg("u") = py::none());
   m.def("_sample_logits_rows", &sample_logits_rows, py::arg("logits"), py::arg("vocab"), py::arg("inv_t"),
         py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("rid"), py::arg("pos"), py::arg("u") = py::none());
+  m.def("_sample_logits_pen", &sample_logits_pen, py::arg("logits"), py::arg("vocab"), py::arg("inv_t"),
+        py::arg("top_k"), py::arg("top_p"), py::arg("seed"), py::arg("rid"), py::arg("rep"), py::arg("inv_rep"),
+        py::arg("pres"), py::arg("freq"), py::arg("hist"), py::arg("pos"), py::arg("u") = py::none(),
+        py::arg("update") = true);
 }

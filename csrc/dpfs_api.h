@@ -256,6 +256,12 @@ void dpfs_sample_logits_rows(const void* logits, int dtype, long long ld, int B,
                              const float* inv_t, const int* top_k, const double* top_p, const int64_t* seed,
                              const int* rid, const int64_t* pos, const float* u_in, int64_t* ids, int* kept,
                              float* thresh, float* u_out, hipStream_t s);
+void dpfs_sample_logits_pen(const void* logits, int dtype, long long ld, int B, int vocab, int vec_ok,
+                            const float* inv_t, const int* top_k, const double* top_p, const int64_t* seed,
+                            const int* rid, const float* rep, const float* inv_rep, const float* pres,
+                            const float* freq, int* hist, long long ld_h, int hist_vec_ok, int update,
+                            const int64_t* pos, const float* u_in, int64_t* ids, int* kept, float* thresh,
+                            float* u_out, float* logp, hipStream_t s);
 
 // comm/rccl_comm.hip
 const char* dpfs_rccl_last_error();

@@ -13,7 +13,10 @@ mutates the token buffer, so TP>1 decoding is correct.  Extensions: ``--syntheti
 (token-id prompts when no tokenizer file is available), the vocab-parallel loss, and sampled
 decoding (``--temperature --top_k --top_p --sample_seed``; the defaults decode greedily;
 ``--per_prompt_seed`` gives prompt i the seed ``sample_seed + i`` and a stream of its own, the
-same one by one and in any batch), and
+same one by one and in any batch; ``--repetition_penalty --presence_penalty
+--frequency_penalty`` penalise the ids of the prompt and of the continuation as ``generate``
+does, and ``--logprobs`` prints the sum and the mean of the model's log-probabilities of the
+generated ids after each completion), and
 ``--decode_batch N``: the prompts are decoded N at a time as one ragged batch (per-row KV
 lengths, ``models/generation.py``) instead of one by one.
 """
@@ -76,6 +79,14 @@ def get_test_args(argv=None):
     g.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling draws")
     g.add_argument("--per_prompt_seed", action="store_true",
                    help="prompt i samples with seed sample_seed + i, whatever batch row decodes it")
+    g.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="> 1 discourages ids of the prompt and the continuation (1: off)")
+    g.add_argument("--presence_penalty", type=float, default=0.0,
+                   help="subtracted once from the logit of every id generated so far (0: off)")
+    g.add_argument("--frequency_penalty", type=float, default=0.0,
+                   help="subtracted from a logit once per time its id was generated (0: off)")
+    g.add_argument("--logprobs", action="store_true",
+                   help="print the sum and mean model log-probability of the generated ids")
     g.add_argument("--decode_batch", type=int, default=1,
                    help="prompts decoded together as one ragged batch (1: one by one, the reference)")
     g.add_argument("--prefill_chunk", type=int, default=0,
@@ -106,7 +117,8 @@ def calc_loss(model: Transformer, dataloader, dev) -> float:
 @torch.inference_mode()
 def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True,
                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                  prefill_chunk: int = 0, kv_dtype=None):
+                  prefill_chunk: int = 0, kv_dtype=None, repetition_penalty=1.0, presence_penalty=0.0,
+                  frequency_penalty=0.0, return_logprobs: bool = False):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
@@ -115,19 +127,26 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
     one-element sequence for the per-row form: ``seed=[s]`` draws with (s, position) alone);
     sampling runs in the KV-cached decode step only.  ``prefill_chunk`` > 0 prefills the prompt
     in pieces of at most that many tokens (KV-cached decoding only); ``kv_dtype`` "fp8" keeps the
-    KV cache as e4m3 codes (``generate``)."""
-    if not kv_cache and (temperature != 0 or isinstance(seed, (list, tuple, torch.Tensor))):
-        raise ValueError("sampling (--temperature > 0) runs in the KV-cached decode step: drop --no_kv_cache")
+    KV cache as e4m3 codes (``generate``).  The three penalties are ``generate``'s (KV-cached
+    decoding only); ``return_logprobs`` returns (ids, the model's log-probability of every
+    generated id, a final EOS included) instead of the ids."""
+    pen = (repetition_penalty, presence_penalty, frequency_penalty) != (1.0, 0.0, 0.0) or return_logprobs
+    if not kv_cache and (temperature != 0 or isinstance(seed, (list, tuple, torch.Tensor)) or pen):
+        raise ValueError("sampling (--temperature > 0), penalties and log-probabilities run in the KV-cached decode "
+                         "step: drop --no_kv_cache")
     if kv_cache:
         from .models.generation import generate
         n0 = 1 + len(prompt_ids)
         tokens = torch.tensor([bos] + list(prompt_ids), dtype=torch.long, device=dev).view(1, -1)
         out = generate(model, tokens, max_new_tokens=max(1, max_len + 1 - n0), eos_id=eos, temperature=temperature,
-                       top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype)[0]
+                       top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype,
+                       repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                       frequency_penalty=frequency_penalty, return_logprobs=return_logprobs)
+        out, lps = (out[0][0], out[1][0]) if return_logprobs else (out[0], None)
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
             out = out[:-1]
-        return out
+        return (out, [a for a, _ in lps]) if return_logprobs else out
     tokens = torch.tensor([bos] + list(prompt_ids), dtype=torch.long, device=dev).view(1, -1)
     while True:
         pos = torch.arange(tokens.size(1), device=dev).unsqueeze(0)
@@ -143,13 +162,16 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
 
 @torch.inference_mode()
 def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
-                        top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None):
+                        top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None,
+                        repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                        return_logprobs: bool = False):
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
     (``seed``, b, position).  Each of ``temperature``, ``top_k``, ``top_p`` and ``seed`` may be a
     sequence with one value per prompt (``generate``): with a seed per prompt, row b draws with
-    (``seed[b]``, position) alone."""
+    (``seed[b]``, position) alone.  The penalties (scalars here) and ``return_logprobs`` are
+    ``greedy_decode``'s: with the latter every prompt gives (ids, model log-probabilities)."""
     from .models.generation import generate
     prompts = [list(p) for p in prompts]
     if not prompts:
@@ -159,25 +181,30 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
         seq = lambda v: isinstance(v, (list, tuple, torch.Tensor))
         row = lambda v, b: [v[b]] if seq(v) else v                # a prompt's own value, still per row
         return [greedy_decode(model, p, bos, eos, max_len, dev, True, row(temperature, b), row(top_k, b),
-                              row(top_p, b), row(seed, b), prefill_chunk, kv_dtype)
+                              row(top_p, b), row(seed, b), prefill_chunk, kv_dtype, repetition_penalty,
+                              presence_penalty, frequency_penalty, return_logprobs)
                 for b, p in enumerate(prompts)]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
         tokens[b, :lens[b]] = torch.tensor([bos] + p, dtype=torch.long, device=dev)
     outs = generate(model, tokens, max_new_tokens=max_len + 1 - min(lens), eos_id=eos, max_len=max_len + 1,
                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, prompt_lens=lens,
-                    prefill_chunk=prefill_chunk, kv_dtype=kv_dtype)
+                    prefill_chunk=prefill_chunk, kv_dtype=kv_dtype, repetition_penalty=repetition_penalty,
+                    presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                    return_logprobs=return_logprobs)
+    outs, lps = outs if return_logprobs else (outs, [None] * len(prompts))
     res = []
-    for p, out in zip(prompts, outs):
+    for p, out, lp in zip(prompts, outs, lps):
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(p):
             out = out[:-1]
-        res.append(out)
+        res.append((out, [a for a, _ in lp]) if return_logprobs else out)
     return res
 
 
 def _decode_all(model, prompts, ds, args, dev, sampling):
-    """Continuations of ``prompts`` (lists of ids): one by one, or ``--decode_batch`` at a time."""
+    """Continuations of ``prompts`` (lists of ids): one by one, or ``--decode_batch`` at a time.
+    With ``--logprobs`` every element is (ids, model log-probabilities of the generated ids)."""
     n = args.decode_batch
     # --per_prompt_seed: prompt i draws with (sample_seed + i, position), one by one and in a batch
     seeds = lambda i, m: {"seed": [sampling["seed"] + j for j in range(i, i + m)]} if args.per_prompt_seed else {}
@@ -233,27 +260,40 @@ def test(rank, args):
                     prefill_chunk=args.prefill_chunk)
     if args.kv_cache_dtype != "act":
         sampling["kv_dtype"] = args.kv_cache_dtype
+    pens = dict(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
+                frequency_penalty=args.frequency_penalty)
+    if pens != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+        sampling.update(pens)
+    if args.logprobs:
+        sampling["return_logprobs"] = True
+    split = lambda outs: zip(*outs) if args.logprobs else (outs, [None] * len(outs))
     decoded = []
     if args.synthetic_prompts or not args.tokenizer_path:
         prompts = [torch.randint(3, margs.vocab_size, (8,), generator=torch.Generator().manual_seed(i)).tolist()
                    for i in range(4)]
-        for ids, out in zip(prompts, _decode_all(model, prompts, ds, args, dev, sampling)):
+        outs, lps = split(_decode_all(model, prompts, ds, args, dev, sampling))
+        for ids, out, lp in zip(prompts, outs, lps):
             assert out[:len(ids)] == ids
-            decoded.append((str(ids), str(out[len(ids):])))
+            decoded.append((str(ids), str(out[len(ids):]), lp))
     else:
         from tokenizers import Tokenizer
         tok = Tokenizer.from_file(args.tokenizer_path)
         assert tok.token_to_id(BOS_TOKEN) == ds.bos and tok.token_to_id(EOS_TOKEN) == ds.eos
         texts = [t.strip() for t in PROMPTS]
-        for t, out in zip(texts, _decode_all(model, [tok.encode(t).ids for t in texts], ds, args, dev, sampling)):
+        outs, lps = split(_decode_all(model, [tok.encode(t).ids for t in texts], ds, args, dev, sampling))
+        for t, out, lp in zip(texts, outs, lps):
             text = tok.decode(out).strip()
-            decoded.append((t, text[len(t):] if text.startswith(t) else text))
+            decoded.append((t, text[len(t):] if text.startswith(t) else text, lp))
     with open(save_path, "a") as fp:
         print("\n\nInput texts -> Decoded texts", file=fp)
-        for a_, b_ in decoded:
-            print(f"{a_} -> {b_}", file=fp)
-            if p.tp_rank == 0:
-                print(f"{a_} -> {b_}", flush=True)
+        for a_, b_, lp in decoded:
+            lines = [f"{a_} -> {b_}"]
+            if lp is not None:      # --logprobs: the model's own distribution, whatever the ids were drawn from
+                lines.append(f"  logprob sum {sum(lp):.4f} mean {sum(lp) / max(1, len(lp)):.4f} over {len(lp)} ids")
+            for line in lines:
+                print(line, file=fp)
+                if p.tp_rank == 0:
+                    print(line, flush=True)
     dist.barrier()
     destroy_dist_env()
     return results
@@ -264,6 +304,9 @@ def main(argv=None):
     if args.no_kv_cache and (args.temperature != 0 or args.per_prompt_seed):
         raise ValueError("sampling (--temperature > 0, --per_prompt_seed) runs in the KV-cached decode step: drop "
                          "--no_kv_cache")
+    if args.no_kv_cache and (args.logprobs or (args.repetition_penalty, args.presence_penalty,
+                                               args.frequency_penalty) != (1.0, 0.0, 0.0)):
+        raise ValueError("penalties and --logprobs run in the KV-cached decode step: drop --no_kv_cache")
     if args.decode_batch < 1 or (args.decode_batch > 1 and args.no_kv_cache):
         raise ValueError("--decode_batch must be >= 1, and > 1 batches the KV-cached decode step: drop --no_kv_cache")
     if args.prefill_chunk < 0 or (args.prefill_chunk > 0 and args.no_kv_cache):

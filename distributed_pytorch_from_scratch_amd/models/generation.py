@@ -26,7 +26,11 @@ Philox draw keyed on (seed, row, position)) inside the same captured step.  The 
 may also be given per row (sequences of B values): the rows of a batch then mix greedy and
 sampled requests of any settings, the values live in a device table of the session
 (``SampleRows``) that the captured ``_sample_logits_rows`` launches read, and a call with new
-settings or seeds is a copy into that table, never a new capture.
+settings or seeds is a copy into that table, never a new capture.  Repetition / presence /
+frequency penalties and log-probabilities run a third form of the launch,
+``_sample_logits_pen``, whose table (``SamplePen``) also holds the token history of every row:
+the launch penalises the logits by it, counts the id it draws into it and writes the id's two
+log-probabilities, all on the device, so penalised steps replay in the same 8-step graphs.
 
 Ragged batches (``generate(..., prompt_lens=...)``): the prompts of a batch may differ in
 length.  The prompt is right-padded; ``cache.len_t`` then holds one int32 per sequence and the
@@ -60,7 +64,7 @@ import torch
 # replay; profiles/r2_decode_bench.jsonl)
 _GRAPH_STEPS = 8
 # captured graphs kept per session (greedy: 2; sampling: 2 per (temperature, top_k, top_p, seed);
-# per-row sampling: 2 for every setting)
+# per-row sampling: 2 for every setting; the penalised form: 2 more for every setting)
 _MAX_GRAPHS = 16
 
 from ..ops import gemm_select as GS
@@ -94,6 +98,7 @@ class KVCache:
         self.lens = [0] * B if ragged else None   # host view of the per-row lengths
         self.t_max = t_max
         self._sample_rows = None          # the per-row sampling settings (device), made on first use
+        self._sample_pen = None           # the same plus penalties and token history, made on first use
 
     @property
     def ragged(self) -> bool:
@@ -116,6 +121,12 @@ class KVCache:
         if self._sample_rows is None:
             self._sample_rows = SampleRows(self.k[0].size(0), self.len_t.device)
         return self._sample_rows
+
+    def sample_pen(self, vocab: int) -> "SamplePen":
+        """The cache's table of the penalised form (settings, penalties, token history)."""
+        if self._sample_pen is None or self._sample_pen.vocab != vocab:
+            self._sample_pen = SamplePen(self.k[0].size(0), vocab, self.len_t.device)
+        return self._sample_pen
 
     def reset(self):
         self.len = 0
@@ -168,6 +179,73 @@ class SampleRows:
         return self
 
 
+class SamplePen(SampleRows):
+    """``SampleRows`` plus what ``_sample_logits_pen`` reads beside it: the penalties ``rep``,
+    ``inv_rep`` = fp32(1 / rep), ``pres`` and ``freq``, fp32 (B,) each, and the token history
+    ``hist`` int32 (B, ld_h), ld_h = vocab rounded up to 8 (whole 16-byte vectors of a bf16 row's
+    layout: B * ld_h * 4 bytes, 201 KB per row of GPT-2's vocabulary).  Bit 31 of ``hist[b, i]``
+    says that id i occurs in row b's prompt, bits 0..30 count the draws of i; the launch itself
+    adds the id it draws, so the table follows the tokens inside a graph replay.  ``logp`` is the
+    (B, 2) log-probability output of the latest launch through ``_draw``."""
+
+    def __init__(self, B: int, vocab: int, device):
+        super().__init__(B, device)
+        self.rep, self.inv_rep, self.pres, self.freq = (torch.zeros(B, dtype=torch.float32, device=device)
+                                                        for _ in range(4))
+        self.vocab = vocab
+        self.hist = torch.zeros(B, (vocab + 7) // 8 * 8, dtype=torch.int32, device=device)
+        self.logp = None
+
+    def pen_tensors(self):
+        return self.tensors() + (self.rep, self.inv_rep, self.pres, self.freq, self.hist)
+
+    def load(self, host) -> "SamplePen":
+        """Copy the nine host lists (``_row_settings`` + ``_penalty_settings``) into the table."""
+        for t, v in zip(self.pen_tensors()[:9], host):
+            t.copy_(torch.tensor(v, dtype=t.dtype))      # (fp64 host values round to fp32 here)
+        return self
+
+    def load_history(self, prompt: torch.Tensor, lens=None) -> "SamplePen":
+        """Zero the history and flag the ids of ``prompt`` (B, T), of ``prompt[b, :lens[b]]`` with
+        ``lens``: once per generate() call, before its first draw."""
+        idx = prompt.long()
+        if lens is not None:    # the padding repeats the row's first id, which is flagged anyway
+            real = torch.arange(idx.size(1), device=idx.device)[None, :] < torch.tensor(lens, device=idx.device)[:, None]
+            idx = torch.where(real, idx, idx[:, :1])
+        self.hist.zero_()
+        self.hist.scatter_(1, idx, -2 ** 31)
+        return self
+
+
+def _penalty_settings(B: int, repetition_penalty, presence_penalty, frequency_penalty):
+    """The penalties of the B rows as four host lists (rep, 1 / rep in fp64, pres, freq; the table
+    rounds them to fp32), scalars broadcast and every value checked; None when every row is
+    neutral (1, 0, 0)."""
+    vals = [repetition_penalty, presence_penalty, frequency_penalty]
+    names = ("repetition_penalty", "presence_penalty", "frequency_penalty")
+    for i, name in enumerate(names):
+        if isinstance(vals[i], (list, tuple, torch.Tensor)):
+            vals[i] = vals[i].tolist() if isinstance(vals[i], torch.Tensor) else list(vals[i])
+            if len(vals[i]) != B:
+                raise ValueError(f"generate: {name} needs one value per sequence ({B}), got {len(vals[i])}")
+        else:
+            vals[i] = [vals[i]] * B
+        vals[i] = [float(v) for v in vals[i]]
+        # (the table holds fp32: a value that overflows it is not finite there)
+        if not all(math.isfinite(v) for v in torch.tensor(vals[i], dtype=torch.float64).float().tolist()):
+            raise ValueError(f"generate: {name} must be finite in fp32 in every row, got {vals[i]}")
+    reps, pres, freq = vals
+    if not all(r > 0 for r in reps):
+        raise ValueError(f"generate: repetition_penalty must be > 0 in every row, got {reps}")
+    inv = [1.0 / r for r in reps]
+    inv32 = torch.tensor(inv, dtype=torch.float64).float().tolist()
+    if not all(math.isfinite(v) and v != 0.0 for v in inv32):
+        raise ValueError(f"generate: fp32(1 / repetition_penalty) must be finite and non-zero, got {reps}")
+    if all(r == 1.0 for r in reps) and all(v == 0.0 for v in pres + freq):
+        return None
+    return reps, inv, pres, freq
+
+
 def _row_settings(B: int, temperature, top_k, top_p, seed):
     """The per-row form of the sampling settings: None when all four are scalars (one setting
     for the batch), else the five host lists of a ``SampleRows`` table, every scalar broadcast
@@ -205,7 +283,13 @@ def _row_settings(B: int, temperature, top_k, top_p, seed):
 
 def _draw(logits: torch.Tensor, vocab: int, sample, pos: torch.Tensor) -> torch.Tensor:
     """Ids (B,) sampled from ``logits`` with ``sample`` = (temperature, top_k, top_p, seed), one
-    ``sample_logits`` launch, or a ``SampleRows`` table, one ``_sample_logits_rows`` launch."""
+    ``sample_logits`` launch, or a ``SampleRows`` table, one ``_sample_logits_rows`` launch, or a
+    ``SamplePen`` table, one ``_sample_logits_pen`` launch, which also counts the ids into the
+    table's history and leaves the two log-probabilities of every id in ``sample.logp``."""
+    if isinstance(sample, SamplePen):
+        out = K(logits)._sample_logits_pen(logits, vocab, *sample.pen_tensors(), pos)
+        sample.logp = out[4]
+        return out[0]
     if isinstance(sample, SampleRows):
         return K(logits)._sample_logits_rows(logits, vocab, *sample.tensors(), pos)[0]
     return K(logits).sample_logits(logits, vocab, *sample, pos)[0]
@@ -464,7 +548,9 @@ class DecodeGraph:
     captured ``sample_logits`` nodes (a session keys its graphs on them), and the draw reads the
     device positions, so a replay at any position draws what the eager step draws there.
     ``sample`` = a ``SampleRows`` table captures ``_sample_logits_rows`` nodes that read the
-    settings from the table at replay: one graph for every setting written there later."""
+    settings from the table at replay: one graph for every setting written there later.
+    ``sample`` = a ``SamplePen`` table captures ``_sample_logits_pen`` nodes, which also read and
+    update the table's token history; step s writes its log-probabilities into ``logps[s]``."""
 
     def __init__(self, model, cache: KVCache, B: int, nsteps: int = 1, sample=None):
         dev = cache.len_t.device
@@ -473,7 +559,11 @@ class DecodeGraph:
         self.ids = torch.zeros(B, 1, dtype=torch.int64, device=dev)
         self.pos = torch.zeros(B, dtype=torch.int64, device=dev)
         self.outs = torch.zeros(nsteps, B, dtype=torch.int64, device=dev)
+        pen = isinstance(sample, SamplePen)
+        # the penalised form: the (model, drawn) log-probabilities of every captured step
+        self.logps = torch.zeros(nsteps, B, 2, dtype=torch.float32, device=dev) if pen else None
         saved = cache.len_t.clone()
+        saved_hist = sample.hist.clone() if pen else None     # the warm-up step counts its id
         # Warm-up off the capture (first-call GEMM choices, allocator pools).  It appends a row
         # at len_t, which the first real step rewrites before anything reads it.
         s = torch.cuda.Stream()
@@ -483,12 +573,16 @@ class DecodeGraph:
             decode_step(model, self.ids, self.pos, cache, sample)
         torch.cuda.current_stream().wait_stream(s)
         cache.len_t.copy_(saved)
+        if pen:
+            sample.hist.copy_(saved_hist)
         _graph_rng_state_normal(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             for i in range(nsteps):
                 nxt, self.logits = decode_step(model, self.ids, self.pos, cache, sample)
                 self.outs[i].copy_(nxt)
+                if pen:
+                    self.logps[i].copy_(sample.logp)
                 if i + 1 < nsteps:
                     self.ids.copy_(nxt.view(-1, 1))
         self.out = self.outs[nsteps - 1]
@@ -562,12 +656,16 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     return cache, graphs
 
 
-def _session_sample(cache: KVCache, sample):
+def _session_sample(cache: KVCache, sample, vocab: int = 0):
     """``sample`` as the decode steps take it, and what names it in a session's graph keys: the
     scalar settings (or None, greedy) themselves; per-row host lists (``_row_settings``) are
-    copied into the cache's table and the key is "rows" whatever they hold."""
+    copied into the cache's table and the key is "rows" whatever they hold; with the four
+    penalty lists behind them (``_penalty_settings``) the table is the ``SamplePen`` one and the
+    key is "pen"."""
     if sample is None or isinstance(sample[0], float):
         return sample, sample
+    if len(sample) == 9:
+        return cache.sample_pen(vocab).load(sample), "pen"
     return cache.sample_rows().load(sample), "rows"
 
 
@@ -580,7 +678,8 @@ def clear_sessions():
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[int] = None,
              max_len: Optional[int] = None, temperature=0.0, top_k=0, top_p=1.0,
              seed=0, prompt_lens=None, prefill_chunk: int = 0,
-             kv_dtype: Optional[str] = None) -> List[List[int]]:
+             kv_dtype: Optional[str] = None, repetition_penalty=1.0, presence_penalty=0.0,
+             frequency_penalty=0.0, return_logprobs: bool = False):
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -610,6 +709,22 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     batch it is decoded.  The settings are device data of the session (``SampleRows``): its two
     per-row graphs are captured once and serve every later setting and seed.
 
+    ``repetition_penalty`` (> 0), ``presence_penalty`` and ``frequency_penalty`` (any finite
+    value), each a scalar or a sequence of B values, penalise the logits before the token choice
+    in the vLLM order (``ops/reference.py:penalised_logits``): a logit whose id occurs in the
+    row's prompt or among its generated ids is divided by the repetition penalty when positive
+    and multiplied by it otherwise; ``frequency_penalty`` times the number of times the id has
+    been generated, and ``presence_penalty`` once if that number is not 0, are subtracted.  The
+    first generated token is penalised (by the prompt) and counted too.  ``return_logprobs=True``
+    returns ``(tokens, logprobs)``: ``logprobs[b]`` holds one ``(logp_model, logp_sampled)`` pair
+    per generated id of row b, the id's log-probability under the model's own distribution (raw
+    logits, temperature 1, no penalty, no filter) and under the distribution it was drawn from.
+    A call with a penalty other than (1, 0, 0) in some row or with ``return_logprobs`` takes the
+    ``_sample_logits_pen`` launch for every row and step: all settings go through the session's
+    ``SamplePen`` table, whose token history the launch itself updates, so the 8-step replays
+    hold; its two graphs, keyed "pen", are captured once for every later setting.  Every other
+    call runs exactly the paths above.
+
     ``prefill_chunk`` > 0 prefills the prompt in pieces of at most that many tokens
     (``logits_step``): the peak activation memory of the call then scales with the piece, not
     with T0.  The decode steps, graphs and sessions are the same; 0 prefills the prompt whole.
@@ -623,7 +738,16 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
     B, T0 = prompt.shape
     dev = prompt.device
-    sample = _row_settings(B, temperature, top_k, top_p, seed)     # host lists; a session's table below
+    pen = _penalty_settings(B, repetition_penalty, presence_penalty, frequency_penalty)
+    if pen is not None or return_logprobs:
+        # the penalised form is per row always: a scalar temperature is broadcast here, and a
+        # scalar seed keeps the row ids 0 .. B - 1 of the scalar call
+        if not isinstance(temperature, (list, tuple, torch.Tensor)):
+            temperature = [temperature] * B
+        sample = _row_settings(B, temperature, top_k, top_p, seed) + (pen or ([1.0] * B, [1.0] * B, [0.0] * B,
+                                                                              [0.0] * B))
+    else:
+        sample = _row_settings(B, temperature, top_k, top_p, seed)     # host lists; a session's table below
     if sample is None:
         if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
             raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
@@ -631,14 +755,19 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
     if prompt_lens is not None:
         return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
-                                sample, prefill_chunk, kv_dtype)
+                                sample, prefill_chunk, kv_dtype, return_logprobs)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype)
     out = [list(map(int, row)) for row in prompt.tolist()]
+    lps = [[] for _ in range(B)]          # (logp_model, logp_sampled) per generated id (the "pen" form)
+    result = lambda: (out, lps) if return_logprobs else out
     done = [False] * B
     if max_new_tokens <= 0 or T0 >= t_max:
-        return out
-    sample, skey = _session_sample(cache, sample)
+        return result()
+    sample, skey = _session_sample(cache, sample, model.vocab_size)
+    pen = isinstance(sample, SamplePen)
+    if pen:
+        sample.load_history(prompt)
     logits = logits_step(model, prompt, cache, prefill_chunk=prefill_chunk)
     if sample is None:
         nxt = logits.argmax(-1)
@@ -650,18 +779,20 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     chunk = _GRAPH_STEPS
     n_gen = 0
 
-    def emit(row) -> bool:
-        """Append one step's ids; True when generation is finished."""
+    def emit(row, lp=None) -> bool:
+        """Append one step's ids (and log-probabilities); True when generation is finished."""
         nonlocal n_gen
         n_gen += 1
         for b, t in enumerate(row):
             if not done[b]:
                 out[b].append(int(t))
+                if lp is not None:
+                    lps[b].append(tuple(lp[b]))
                 done[b] = eos_id is not None and int(t) == eos_id
         return all(done) or n_gen >= max_new_tokens or cache.len >= t_max
 
-    if emit(nxt.tolist()):
-        return out
+    if emit(nxt.tolist(), sample.logp.tolist() if pen else None):
+        return result()
     while True:
         if _use_graph(dev):
             # S steps per replay while S more tokens are wanted and the cache has room for them
@@ -676,20 +807,21 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
             g.pos.fill_(cache.len)
             outs = g.step(nxt)
             rows = outs.tolist()
+            lrows = g.logps.tolist() if pen else [None] * S
             nxt = g.out
-            for row in rows:
+            for row, lp in zip(rows, lrows):
                 cache.len += 1
-                if emit(row):
-                    return out
+                if emit(row, lp):
+                    return result()
         else:
             nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
             cache.len += 1
-            if emit(nxt.tolist()):
-                return out
+            if emit(nxt.tolist(), sample.logp.tolist() if pen else None):
+                return result()
 
 
 def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
-                     prefill_chunk: int = 0, kv_dtype: Optional[str] = None):
+                     prefill_chunk: int = 0, kv_dtype: Optional[str] = None, return_logprobs: bool = False):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
     that has filled the cache frozen inside it (``_step_advance_rows``)."""
@@ -700,10 +832,15 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype)
     rows = prompt.tolist()
     out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
+    lps = [[] for _ in range(B)]
+    result = lambda: (out, lps) if return_logprobs else out
     done = [n >= cap for n in lens]
     if max_new_tokens <= 0 or all(done):
-        return out
-    sample, skey = _session_sample(cache, sample)
+        return result()
+    sample, skey = _session_sample(cache, sample, model.vocab_size)
+    pen = isinstance(sample, SamplePen)
+    if pen:
+        sample.load_history(prompt, lens)
     # The padded prompt up to the longest row that fits the cache; a row at or past the cache
     # capacity is done already and enters the cache full (frozen).
     T = min(max(lens), t_max)
@@ -719,18 +856,21 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     chunk = _GRAPH_STEPS
     n_gen = 0
 
-    def emit(row) -> bool:
-        """Append one step's ids to the live rows; True when every row is finished."""
+    def emit(row, lp=None) -> bool:
+        """Append one step's ids (and log-probabilities) to the live rows; True when every row is
+        finished."""
         nonlocal n_gen
         n_gen += 1
         for b, t in enumerate(row):
             if not done[b]:
                 out[b].append(int(t))
+                if lp is not None:
+                    lps[b].append(tuple(lp[b]))
                 done[b] = (eos_id is not None and int(t) == eos_id) or len(out[b]) >= cap
         return all(done) or n_gen >= max_new_tokens
 
-    if emit(nxt.tolist()):
-        return out
+    if emit(nxt.tolist(), sample.logp.tolist() if pen else None):
+        return result()
     while True:
         if _use_graph(dev):
             # S steps per replay while S more tokens are wanted and the longest live row has room
@@ -747,13 +887,14 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
             g.pos.copy_(cache.device_pos())
             outs = g.step(nxt)
             steps = outs.tolist()
+            lsteps = g.logps.tolist() if pen else [None] * S
             nxt = g.out
-            for row in steps:
+            for row, lp in zip(steps, lsteps):
                 cache.advance()
-                if emit(row):
-                    return out
+                if emit(row, lp):
+                    return result()
         else:
             nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
             cache.advance()
-            if emit(nxt.tolist()):
-                return out
+            if emit(nxt.tolist(), sample.logp.tolist() if pen else None):
+                return result()

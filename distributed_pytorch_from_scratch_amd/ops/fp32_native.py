@@ -91,8 +91,8 @@ def gemv_nt_ok(x, w, swiglu: bool = False) -> bool:
 
 
 # single-token decode (models/generation.py): bf16 kernels only; fp32 decode on tensor ops
-# (the token choice, sample_logits / _sample_logits_rows, takes fp32 rows too and reaches the
-# kernel through __getattr__ below)
+# (the token choice, sample_logits / _sample_logits_rows / _sample_logits_pen, takes fp32 rows
+# too and reaches the kernel through __getattr__ below)
 attn_decode = reference.attn_decode
 kv_append = reference.kv_append
 rope_append = reference.rope_append

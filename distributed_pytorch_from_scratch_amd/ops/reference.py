@@ -509,6 +509,66 @@ def sample_logits_rows(logits: torch.Tensor, vocab: int, inv_t: torch.Tensor, to
 _sample_logits_rows = sample_logits_rows
 
 
+def penalised_logits(logits: torch.Tensor, vocab: int, rep: torch.Tensor, inv_rep: torch.Tensor, pres: torch.Tensor,
+                     freq: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """The fp32 (B, vocab) row ``sample_logits_pen`` samples from.  ``hist`` int32 (B, >= vocab):
+    bit 31 of a word says that the id occurs in the row's prompt, bits 0..30 are c, the number of
+    times it has been drawn; seen = word != 0.  In the vLLM order (repetition over prompt and
+    output, presence and frequency over the output only), every step one rounded fp32 operation:
+
+        x = fp32(logit);  seen: x = x * inv_rep if x > 0 else x * rep;  x = x - freq * fp32(c);
+        c > 0: x = x - pres."""
+    x = logits[:, :vocab].float()
+    h = hist[:, :vocab]
+    c = h & 0x7FFFFFFF
+    col = lambda t: t.to(torch.float32)[:, None]
+    x = torch.where(h != 0, torch.where(x > 0, x * col(inv_rep), x * col(rep)), x)
+    x = x - col(freq) * c.to(torch.float32)
+    return torch.where(c > 0, x - col(pres), x)
+
+
+def sample_logprobs_fp64(logits: torch.Tensor, vocab: int, x: torch.Tensor, inv_t: torch.Tensor,
+                         thresh: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """The two log-probabilities of ``sample_logits_pen`` before their rounding to fp32, fp64
+    (B, 2): of ids[b] under softmax(raw logits), and under the distribution drawn from, the
+    weights exp(z - max z), z = fp32(x * inv_t), of the kept columns {x >= thresh} of the
+    penalised row ``x`` (a greedy row: z = 0, every maximum weighs 1)."""
+    at = ids[:, None]
+    lp_model = torch.log_softmax(logits[:, :vocab].double(), -1).gather(-1, at)[:, 0]
+    z = (x * inv_t[:, None]).double()
+    z = z - z.max(-1, keepdim=True).values
+    mass = (torch.exp(z) * (x >= thresh[:, None])).sum(-1)
+    return torch.stack([lp_model, z.gather(-1, at)[:, 0] - torch.log(mass)], -1)
+
+
+def sample_logits_pen(logits: torch.Tensor, vocab: int, inv_t: torch.Tensor, top_k: torch.Tensor,
+                      top_p: torch.Tensor, seed: torch.Tensor, rid: torch.Tensor, rep: torch.Tensor,
+                      inv_rep: torch.Tensor, pres: torch.Tensor, freq: torch.Tensor, hist: torch.Tensor,
+                      pos: torch.Tensor, u: Optional[torch.Tensor] = None, update: bool = True):
+    """``sample_logits_rows`` on ``penalised_logits`` (x in place of the logit everywhere: z =
+    x * inv_t, top-k / top-p / ties, the greedy first maximum; ``kept`` and ``thresh`` in units of
+    x), with the penalties ``rep`` / ``inv_rep`` = fp32(1 / rep, the quotient in fp64) / ``pres`` /
+    ``freq`` fp32 (B,) and the history ``hist`` int32 (B, >= vocab) as data.  Returns (ids, kept,
+    thresh, u, logp, hist): ``logp`` fp32 (B, 2), computed in fp64, holds the log-probability of
+    ids[b] under the model's own distribution (softmax of the raw logits: temperature 1, no
+    penalty, no filter) and under the distribution the draw used (log of the id's share of the
+    kept, penalised, tempered mass; -log(number of maxima) on a greedy row).  With ``update``
+    hist[b, ids[b]] += 1, in place as the kernel does it; the table is returned either way."""
+    B = logits.size(0)
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.size(0) == B and hist.size(1) >= vocab
+    for t in (rep, inv_rep, pres, freq):
+        assert t.dtype == torch.float32 and t.shape == (B,), "one fp32 penalty per row"
+    x = penalised_logits(logits, vocab, rep, inv_rep, pres, freq, hist)
+    ids, kept, thresh, uo = sample_logits_rows(x, vocab, inv_t, top_k, top_p, seed, rid, pos, u)
+    logp = sample_logprobs_fp64(logits, vocab, x, inv_t, thresh, ids).float()
+    if update:
+        hist[torch.arange(B, device=hist.device), ids] += 1
+    return ids, kept, thresh, uo, logp, hist
+
+
+_sample_logits_pen = sample_logits_pen
+
+
 def _rot_bthd(x: torch.Tensor, positions: torch.Tensor, table: torch.Tensor, inverse: bool) -> torch.Tensor:
     """Rotate-half RoPE of an fp32 (B, T, H, hd) tensor; ``positions`` is flat [B*T]."""
     B, T, H, hd = x.shape

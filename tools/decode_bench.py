@@ -7,6 +7,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
                                  [--ragged | --ragged-equal]
                                  [--prefill-chunk N [N ...]] [--continuation --t0 1024 --chunk 256]
                                  [--kv-dtype {act,fp8,both}] [--modes graph eager]
+                                 [--penalties R,P,F] [--logprobs]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -39,6 +40,12 @@ assignment, fp32 einsum / softmax / einsum over the whole cache), in interleaved
 the activation-dtype cache and the fp8 cache in interleaved rounds (``--repeats`` of them, each
 dtype's session warm) and adds one line per (batch, mode, dtype) with the median and the kept
 session's cache bytes.  ``--modes`` restricts the run to the graph or the eager step.
+
+``--penalties R,P,F`` (repetition, presence, frequency) and ``--logprobs`` add the penalised form
+of the sampling launch (``generate(..., repetition_penalty=R, ..., return_logprobs=True)``) to the
+same interleaved rounds: every round then times the call as the other flags give it and the same
+call with the penalties / log-probabilities, and the lines of the latter carry ``"form": "pen"``.
+``--sample-kernel --penalties R,P,F`` times the ``_sample_logits_pen`` launch alone.
 """
 from __future__ import annotations
 
@@ -76,7 +83,17 @@ def main():
     ap.add_argument("--kv-dtype", choices=["act", "fp8", "both"], default="act",
                     help="KV cache storage: activation dtype, fp8 codes, or both in interleaved rounds")
     ap.add_argument("--modes", nargs="+", choices=["graph", "eager"], default=["graph", "eager"])
+    ap.add_argument("--penalties", default=None, metavar="R,P,F",
+                    help="repetition,presence,frequency: also time the penalised form in the same rounds")
+    ap.add_argument("--logprobs", action="store_true", help="the penalised form returns log-probabilities")
     a = ap.parse_args()
+    pen_kw = {}
+    if a.penalties:
+        r, p_, f = (float(v) for v in a.penalties.split(","))
+        pen_kw = dict(repetition_penalty=r, presence_penalty=p_, frequency_penalty=f)
+    if a.logprobs:
+        pen_kw["return_logprobs"] = True
+    forms = [("base", {})] + ([("pen", pen_kw)] if pen_kw else [])
     sampling = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=0)
     fresh = (a.seeds or ("fresh" if a.per_row else "fixed")) == "fresh"
     calls = [0]
@@ -122,20 +139,24 @@ def main():
         for mode in a.modes:
             os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
             for kd in kds:
-                # warm-up: GEMM choices, graph capture (reused by the same-shape call)
-                generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **settings(B), **kw)
+                for _, fkw in forms:
+                    # warm-up: GEMM choices, graph capture (reused by the same-shape call)
+                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **settings(B), **kw, **fkw)
             ms = {kd: [] for kd in kds}
             for _ in range(a.repeats):
-                for kd in kds:                                      # interleaved rounds
+                for kd, (form, fkw) in ((kd, f) for kd in kds for f in forms):      # interleaved rounds
                     st = settings(B)
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **st, **kw)
+                    generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, **st, **kw, **fkw)
                     torch.cuda.synchronize()
                     dt = time.perf_counter() - t0
-                    ms[kd].append(round(1000 * dt / a.new, 3))
+                    if form == "base":
+                        ms[kd].append(round(1000 * dt / a.new, 3))
                     rec = {"model": a.model, "batch": B, "mode": mode, "prompt": a.prompt, "new": a.new,
                            "ms_per_step": round(1000 * dt / a.new, 3), "tokens_per_s": round(B * a.new / dt, 1)}
+                    if form == "pen":
+                        rec.update(form="pen", penalties=a.penalties, logprobs=a.logprobs)
                     if a.kv_dtype != "act":
                         rec["kv_dtype"] = kd or "act"
                     if lens:
@@ -169,7 +190,7 @@ def main():
                                   "ragged": "spread", "min_len": min(lens), "max_len": max(lens),
                                   "ms_per_step": round(1000 * dt / (B * a.new), 3),
                                   "tokens_per_s": round(B * a.new / dt, 1)}), flush=True)
-        if a.temperature > 0 or a.per_row or lens:
+        if a.temperature > 0 or a.per_row or lens or pen_kw:
             continue
         # reference formulation: every token re-runs the whole prefix (no cache)
         seq = prompt
@@ -302,7 +323,9 @@ def continuation_bench(a, m):
 
 def sample_kernel_bench(a, ld: int, vocab: int):
     """us per ``sample_logits`` launch (``--per-row``: ``_sample_logits_rows`` with the same
-    settings in every row of its table) on (B, ld) bf16 rows: device events over 200 launches."""
+    settings in every row of its table; ``--penalties``: ``_sample_logits_pen`` with them, on a
+    history of 128 prompt flags per row that the 200 launches count into) on (B, ld) bf16 rows:
+    device events over 200 launches."""
     import torch
     from distributed_pytorch_from_scratch_amd.ops import _ext
     C = _ext.require()
@@ -310,12 +333,18 @@ def sample_kernel_bench(a, ld: int, vocab: int):
     for B in a.batch:
         x = (torch.randn(B, ld, device="cuda") * 4).bfloat16()
         pos = torch.zeros(B, dtype=torch.int64, device="cuda")
-        if a.per_row:
+        if a.per_row or a.penalties:
             tab = (torch.full((B,), 1.0 / T, dtype=torch.float64).float().cuda(),
                    torch.full((B,), a.top_k, dtype=torch.int32, device="cuda"),
                    torch.full((B,), a.top_p, dtype=torch.float64, device="cuda"),
                    torch.zeros(B, dtype=torch.int64, device="cuda"), torch.arange(B, dtype=torch.int32, device="cuda"))
             launch = lambda: C._sample_logits_rows(x, vocab, *tab, pos)
+            if a.penalties:
+                r, p_, f = (float(v) for v in a.penalties.split(","))
+                pens = [torch.full((B,), v, dtype=torch.float64).float().cuda() for v in (r, 1.0 / r, p_, f)]
+                hist = torch.zeros(B, (vocab + 7) // 8 * 8, dtype=torch.int32, device="cuda")
+                hist.scatter_(1, torch.randint(0, vocab, (B, 128), device="cuda"), -2 ** 31)
+                launch = lambda: C._sample_logits_pen(x, vocab, *tab, *pens, hist, pos)
         else:
             launch = lambda: C.sample_logits(x, vocab, T, a.top_k, a.top_p, 0, pos)
         # 200 launches in one graph: the replay is not paced by the host's launch rate
@@ -336,7 +365,8 @@ def sample_kernel_bench(a, ld: int, vocab: int):
             g.replay()
             e1.record()
             torch.cuda.synchronize()
-            print(json.dumps({"kernel": "sample_logits_rows" if a.per_row else "sample_logits", "batch": B,
+            name = "sample_logits_pen" if a.penalties else "sample_logits_rows" if a.per_row else "sample_logits"
+            print(json.dumps({"kernel": name, "batch": B,
                               "vocab": vocab, "ld": ld, "temperature": T, "top_k": a.top_k, "top_p": a.top_p,
                               "us_per_call": round(5 * e0.elapsed_time(e1), 2)}),
                   flush=True)
