@@ -276,6 +276,158 @@ void rope_append_q8(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, t
                       (int)c.B, (int)c.H, (int)c.hd, (int)c.Tmax, stream());
 }
 
+// -------------------------------------------------------------------- paged KV cache --
+// The layout of kernels/kv_page.h: pools (P, page, H, hd) per side, bf16 (ks / vs none) or
+// float8_e4m3fn with fp32 scale pools ks / vs (P, page, H); tbl int32 (B, MP), MP = ceil(t_max /
+// page), entry -1 = unmapped; len int32 [B] (a paged cache is per-row).  Shapes, dtypes and the page
+// size are checked here; the table's content is device data that the kernels are safe against
+// (a store through an entry outside [0, P) is dropped, a load is redirected inside the pool), so
+// nothing here reads it and nothing synchronises.  Bound with leading underscores and recorded in
+// tests/golden/ext_api_paged.txt (tests/test_ext_api_paged.py).
+struct PagedShape {
+  int64_t B, MP, P, PS, H, hd;
+  int lg;
+  float *ks, *vs;   // null: bf16 pools
+};
+
+PagedShape check_paged(const torch::Tensor& kp, const torch::Tensor& vp, const c10::optional<torch::Tensor>& ks,
+                       const c10::optional<torch::Tensor>& vs, const torch::Tensor& tbl, const torch::Tensor& len,
+                       int64_t t_max, int64_t page, const char* op) {
+  TORCH_CHECK(page >= 16 && page <= 256 && (page & (page - 1)) == 0, op,
+              ": the page size must be a power of two in [16, 256], got ", page);
+  TORCH_CHECK(ks.has_value() == vs.has_value(), op, ": ks and vs are given together (fp8 pools) or not at all");
+  const bool q8 = ks.has_value();
+  const auto want = q8 ? at::kFloat8_e4m3fn : at::kBFloat16;
+  for (const torch::Tensor* c : {&kp, &vp}) {
+    check_cuda(*c, "pool");
+    TORCH_CHECK(c->dim() == 4 && c->is_contiguous() && c->scalar_type() == want && c->size(1) == page, op,
+                ": k_pool / v_pool must be contiguous ", want, " (P, page = ", page, ", H, hd) pools, got ", c->sizes(),
+                " of ", c->scalar_type());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": pools must be 16-byte aligned");
+  }
+  TORCH_CHECK(kp.sizes() == vp.sizes() && kp.device() == vp.device(), op, ": k_pool / v_pool differ");
+  PagedShape s{0, 0, kp.size(0), page, kp.size(2), kp.size(3), 0, nullptr, nullptr};
+  while ((1LL << s.lg) < page) ++s.lg;
+  TORCH_CHECK(s.hd == 32 || s.hd == 64 || s.hd == 128, op, ": head_dim 32, 64 or 128");
+  TORCH_CHECK(s.P >= 1 && s.P * s.PS < (1LL << 31), op, ": the pool needs 1 <= P and P * page < 2^31 rows");
+  if (q8) {
+    for (const torch::Tensor* c : {&*ks, &*vs}) {
+      check_cuda(*c, "pool scales");
+      TORCH_CHECK(c->dim() == 3 && c->is_contiguous() && c->scalar_type() == torch::kFloat32 && c->size(0) == s.P &&
+                      c->size(1) == s.PS && c->size(2) == s.H && c->device() == kp.device(),
+                  op, ": ks / vs must be contiguous fp32 (P, page, H) scale pools");
+    }
+    s.ks = ks->data_ptr<float>();
+    s.vs = vs->data_ptr<float>();
+  }
+  TORCH_CHECK(t_max >= 1 && t_max < (1LL << 30), op, ": t_max must be in [1, 2^30), got ", t_max);
+  check_cuda(tbl, "tbl");
+  TORCH_CHECK(tbl.scalar_type() == torch::kInt32 && tbl.dim() == 2 && tbl.is_contiguous() && tbl.size(0) >= 1 &&
+                  tbl.size(1) == (t_max + page - 1) / page && tbl.device() == kp.device(),
+              op, ": tbl must be a contiguous device int32 (B, MP = ceil(t_max / page) = ", (t_max + page - 1) / page,
+              ") table, got ", tbl.sizes(), " of ", tbl.scalar_type());
+  s.B = tbl.size(0);
+  s.MP = tbl.size(1);
+  check_cuda(len, "len");
+  TORCH_CHECK(len.scalar_type() == torch::kInt32 && len.is_contiguous() && len.numel() == s.B &&
+                  len.device() == kp.device(),
+              op, ": len must be a contiguous device int32 tensor of B = ", s.B, " elements (a paged cache is per-row)");
+  return s;
+}
+
+// attn_decode (per-row form) / _attn_decode_q8 through a block table: same grid, splits and math
+// over the logical key index, so the output equals the contiguous launch on the same cache
+// content bit for bit.
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, c10::optional<torch::Tensor> ks,
+                                c10::optional<torch::Tensor> vs, torch::Tensor tbl, torch::Tensor len, int64_t t_max,
+                                int64_t page, double scale) {
+  check_rowmajor(q, "q");
+  const PagedShape c = check_paged(kp, vp, ks, vs, tbl, len, t_max, page, "attn_decode_paged");
+  TORCH_CHECK(q.size(0) == c.B && q.size(1) >= c.H * c.hd && q.stride(0) % 8 == 0 &&
+                  q.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_decode_paged: q rows");
+  TORCH_CHECK(c.B * c.H <= 65535, "attn_decode_paged: shape too large");
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({c.B, c.H * c.hd}, q.options());
+  const int ns = dpfs_decode_nsplit((int)t_max);
+  auto part = torch::empty({c.B * c.H * ns * (c.hd + 2)}, q.options().dtype(torch::kFloat32));
+  dpfs_attn_decode_paged(q.data_ptr(), q.stride(0), kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(),
+                         (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), o.data_ptr(), c.H * c.hd,
+                         part.data_ptr<float>(), (int)c.B, (int)c.H, (int)c.hd, (int)t_max, (float)scale, stream());
+  return o;
+}
+
+// rope_append (per-row form) / _rope_append_q8 through a block table.
+void rope_append_paged(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kp, torch::Tensor vp,
+                       c10::optional<torch::Tensor> ks, c10::optional<torch::Tensor> vs, torch::Tensor tbl,
+                       torch::Tensor len, int64_t t_max, int64_t page) {
+  check_rowmajor(qkv, "qkv");
+  const PagedShape c = check_paged(kp, vp, ks, vs, tbl, len, t_max, page, "rope_append_paged");
+  TORCH_CHECK(qkv.size(0) == c.B && qkv.size(1) == 3 * c.H * c.hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "rope_append_paged: qkv must be [B, 3*H*hd] bf16, row stride % 8 == 0, 16-byte aligned");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt64 && pos.is_contiguous() && pos.numel() == c.B,
+              "rope_append_paged: pos must be contiguous int64 [B]");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kFloat32 && table.is_contiguous() &&
+                  table.dim() == 2 && table.size(1) == c.hd,
+              "rope_append_paged: table must be fp32 [maxlen, hd]");
+  TORCH_CHECK(c.B * c.H * c.hd < (1LL << 27), "rope_append_paged: shape too large");
+  const at::DeviceGuard g(qkv.device());
+  if (c.ks)
+    dpfs_rope_append_q8_paged(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(), table.data_ptr<float>(),
+                              kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(), (int)c.MP, (int)c.P, c.lg,
+                              len.data_ptr<int>(), (int)c.B, (int)c.H, (int)c.hd, (int)t_max, stream());
+  else
+    dpfs_rope_append_paged(qkv.data_ptr(), qkv.stride(0), pos.data_ptr<int64_t>(), table.data_ptr<float>(),
+                           kp.data_ptr(), vp.data_ptr(), tbl.data_ptr<int>(), (int)c.MP, (int)c.P, c.lg,
+                           len.data_ptr<int>(), (int)c.B, (int)c.H, (int)c.hd, (int)t_max, stream());
+}
+
+// _kv_append_chunk / _kv_append_chunk_q8 through a block table.
+void kv_append_chunk_paged(torch::Tensor qkv, torch::Tensor kp, torch::Tensor vp, c10::optional<torch::Tensor> ks,
+                           c10::optional<torch::Tensor> vs, torch::Tensor tbl, torch::Tensor len,
+                           c10::optional<torch::Tensor> n, int64_t t_max, int64_t page) {
+  check_rowmajor(qkv, "qkv");
+  const PagedShape c = check_paged(kp, vp, ks, vs, tbl, len, t_max, page, "kv_append_chunk_paged");
+  TORCH_CHECK(qkv.size(0) % c.B == 0 && qkv.size(0) >= c.B && qkv.size(1) == 3 * c.H * c.hd && qkv.stride(0) % 8 == 0 &&
+                  qkv.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "kv_append_chunk_paged: qkv must be [B*T, 3*H*hd] bf16, row stride % 8 == 0, 16-byte aligned");
+  const int64_t T = qkv.size(0) / c.B;
+  TORCH_CHECK(c.B * T < (1LL << 31) && c.B * T * c.H * (c.hd / 8) < (1LL << 40), "kv_append_chunk_paged: shape too large");
+  const int* np = check_chunk_n(n, c.B, qkv);
+  const at::DeviceGuard g(qkv.device());
+  const char* p = static_cast<const char*>(qkv.data_ptr());
+  if (c.ks)
+    dpfs_kv_append_chunk_q8_paged(p + c.H * c.hd * 2, p + 2 * c.H * c.hd * 2, qkv.stride(0), kp.data_ptr(),
+                                  vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(), (int)c.MP, (int)c.P, c.lg,
+                                  len.data_ptr<int>(), np, (int)c.B, (int)T, (int)c.H, (int)c.hd, (int)t_max, stream());
+  else
+    dpfs_kv_append_chunk_paged(p + c.H * c.hd * 2, p + 2 * c.H * c.hd * 2, qkv.stride(0), kp.data_ptr(), vp.data_ptr(),
+                               tbl.data_ptr<int>(), (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), np, (int)c.B,
+                               (int)T, (int)c.H, (int)c.hd, (int)t_max, stream());
+}
+
+// _attn_extend / _attn_extend_q8 through a block table (the pools already hold the chunk's rows):
+// the same tiles over the logical key index, bit-identical to the contiguous launch.
+torch::Tensor attn_extend_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, c10::optional<torch::Tensor> ks,
+                                c10::optional<torch::Tensor> vs, torch::Tensor tbl, torch::Tensor len,
+                                c10::optional<torch::Tensor> n, int64_t t_max, int64_t page, double scale) {
+  check_rowmajor(q, "q");
+  const PagedShape c = check_paged(kp, vp, ks, vs, tbl, len, t_max, page, "attn_extend_paged");
+  TORCH_CHECK(q.size(0) % c.B == 0 && q.size(0) >= c.B && q.size(1) >= c.H * c.hd && q.stride(0) % 8 == 0 &&
+                  q.scalar_type() == torch::kBFloat16 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_extend_paged: q must be bf16 rows [B*T, >= H*hd], row stride % 8 == 0, 16-byte aligned");
+  const int64_t T = q.size(0) / c.B;
+  TORCH_CHECK(c.B * c.H <= 65535 && c.B * T * c.H * c.hd < (1LL << 31), "attn_extend_paged: shape too large");
+  const int* np = check_chunk_n(n, c.B, q);
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({c.B * T, c.H * c.hd}, q.options());
+  dpfs_attn_extend_paged(q.data_ptr(), q.stride(0), kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(),
+                         (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), np, o.data_ptr(), (int)c.B, (int)T, (int)c.H,
+                         (int)c.hd, (int)t_max, (float)scale, stream());
+  return o;
+}
+
 // Per-tensor fp8 quantisation with current scaling: (q, inv) with q = sat(x * FMAX / amax)
 // in float8_e4m3fn (fmt 0) or float8_e5m2 (fmt 1), inv = amax / FMAX as an fp32 0-d tensor
 // (the scale torch._scaled_mm multiplies back).  No host synchronisation.
@@ -503,6 +655,16 @@ void bind_decode(py::module_& m) {
         py::arg("vs"), py::arg("len"), py::arg("n") = py::none());
   m.def("_rope_append_q8", &rope_append_q8, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k8"),
         py::arg("v8"), py::arg("ks"), py::arg("vs"), py::arg("len"));
+  m.def("_attn_decode_paged", &attn_decode_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("ks"),
+        py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("t_max"), py::arg("page"), py::arg("scale"));
+  m.def("_rope_append_paged", &rope_append_paged, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("ks"), py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("t_max"),
+        py::arg("page"));
+  m.def("_kv_append_chunk_paged", &kv_append_chunk_paged, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("ks"), py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("n"), py::arg("t_max"), py::arg("page"));
+  m.def("_attn_extend_paged", &attn_extend_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("ks"),
+        py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("n"), py::arg("t_max"), py::arg("page"),
+        py::arg("scale"));
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);

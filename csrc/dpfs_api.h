@@ -46,6 +46,14 @@ void dpfs_kv_append_chunk(const void* ksrc, const void* vsrc, long long ld, void
 void dpfs_attn_extend_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
                          const float* vs, const int* len, int len_rows, const int* n, void* o, int B, int T, int H,
                          int HD, int Tmax, float scale, hipStream_t s);
+// paged KV cache (kernels/kv_page.h): pools kp / vp (P, PS, H, HD), tbl (B, MP) int32, PS = 1 << lg, len[B];
+// ks / vs null: bf16 pools, else e4m3 pools with fp32 scale pools (P, PS, H)
+void dpfs_attn_extend_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
+                            const float* vs, const int* tbl, int MP, int P, int lg, const int* len, const int* n,
+                            void* o, int B, int T, int H, int HD, int Tmax, float scale, hipStream_t s);
+void dpfs_kv_append_chunk_paged(const void* ksrc, const void* vsrc, long long ld, void* kp, void* vp, const int* tbl,
+                                int MP, int P, int lg, const int* len, const int* n, int B, int T, int H, int HD,
+                                int Tmax, hipStream_t s);
 
 // kernels/attention_fused.hip
 void dpfs_attn_bwd_dkdv4(int items, const void* q, const void* k, const void* v, const void* dout, const float* lsn,
@@ -85,6 +93,14 @@ void dpfs_step_advance_rows(int* len, int64_t* pos, int B, int t_max, hipStream_
 void dpfs_attn_decode_q8(const void* q, long long ldq, const void* k8, const void* v8, const float* ks,
                          const float* vs, const int* len, int len_rows, void* o, long long ldo, float* part, int B,
                          int H, int HD, int Tmax, float scale, hipStream_t s);
+// paged KV cache (kernels/kv_page.h): pools kp / vp (P, PS, H, HD), tbl (B, MP) int32, PS = 1 << lg, len[B];
+// ks / vs null: bf16 pools, else e4m3 pools with fp32 scale pools (P, PS, H)
+void dpfs_attn_decode_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
+                            const float* vs, const int* tbl, int MP, int P, int lg, const int* len, void* o,
+                            long long ldo, float* part, int B, int H, int HD, int Tmax, float scale, hipStream_t s);
+void dpfs_rope_append_paged(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kp, void* vp,
+                            const int* tbl, int MP, int P, int lg, const int* len, int B, int H, int HD, int Tmax,
+                            hipStream_t s);
 
 // kernels/elementwise.hip
 void dpfs_swiglu_fwd(int dtype, const void* gu, void* h, int M, int F, int perm, hipStream_t s);
@@ -234,6 +250,13 @@ void dpfs_kv_append_chunk_q8(const void* ksrc, const void* vsrc, long long ld, v
                              int Tmax, hipStream_t s);
 void dpfs_rope_append_q8(void* qkv, long long ld, const int64_t* pos, const float* tab, void* k8, void* v8, float* ks,
                          float* vs, const int* len, int len_rows, int B, int H, int HD, int Tmax, hipStream_t s);
+// paged KV cache (kernels/kv_page.h): e4m3 pools kp / vp (P, PS, H, HD) with fp32 scale pools ks / vs (P, PS, H)
+void dpfs_kv_append_chunk_q8_paged(const void* ksrc, const void* vsrc, long long ld, void* kp, void* vp, float* ks,
+                                   float* vs, const int* tbl, int MP, int P, int lg, const int* len, const int* n,
+                                   int B, int T, int H, int HD, int Tmax, hipStream_t s);
+void dpfs_rope_append_q8_paged(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kp, void* vp,
+                               float* ks, float* vs, const int* tbl, int MP, int P, int lg, const int* len, int B,
+                               int H, int HD, int Tmax, hipStream_t s);
 
 // kernels/norm.hip
 int dpfs_norm_bwd_grid(int M);

@@ -33,8 +33,14 @@
 // A-operand row) and the V chunks staged to LDS bf16_rn(f32(code) * vs[row]), so the kernel
 // equals, bit for bit, the bf16 form run on caches dequantised to bf16 by that expression.  The
 // prefetched tile is held as codes (half the registers of the bf16 prefetch).
+//
+// Paged KV cache (PAGED = true; the layout and its safety contract are in kv_page.h): the caches
+// are pools addressed through a block table.  Tiles, waves and the merge stay on the logical key
+// index; only the K-row and V-chunk fetches differ, each lane looking up the pool row of the key
+// it loads, so the output equals the contiguous launch on the same cache content bit for bit.
 #include "common.h"
 #include "kv8.h"
+#include "kv_page.h"
 #include "../dpfs_api.h"
 #include "attn_common.h"
 
@@ -51,13 +57,14 @@ __device__ __forceinline__ int ext_swz(int r, int ch) {
   return HD == 64 ? (ch ^ (((r >> 1) & 1) << 2)) : (ch ^ ((r & 3) << 2));
 }
 
-template <int HD, bool Q8 = false>
+template <int HD, bool Q8 = false, bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q, long long ldq,
                                                      const void* __restrict__ kcv, const void* __restrict__ vcv,
                                                      const float* __restrict__ ksc, const float* __restrict__ vsc,
                                                      const int* __restrict__ len_ptr, int len_rows,
                                                      const int* __restrict__ n_ptr, bf16* __restrict__ o, int T,
-                                                     int H, int Tmax, float scale) {
+                                                     int H, int Tmax, float scale, PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
   constexpr int KS = HD / 16, DTN = HD / 32, RB = HD * 2, CPR = HD / 8;
   constexpr int VT = kExtK * RB;             // a wave's V tile
   constexpr int NVC = kExtK * CPR / 64;      // 16-byte V chunks per lane per tile
@@ -107,12 +114,19 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
   // the last key of this lane's query, relative to its first key row of a tile (4 hf)
   const int qlim = (live ? len + tq : -1) - 4 * hf;
 
-  const bf16* kbase = (const bf16*)kcv + ((long long)b * Tmax * H + h) * HD;
-  const bf16* vbase = (const bf16*)vcv + ((long long)b * Tmax * H + h) * HD;
-  const uint8_t* k8base = (const uint8_t*)kcv + ((long long)b * Tmax * H + h) * HD;
-  const uint8_t* v8base = (const uint8_t*)vcv + ((long long)b * Tmax * H + h) * HD;
-  const long long sbase = (long long)b * Tmax * H + h;   // scale of key row k: sbase + k * H
+  // PAGED: the bases are the pools' (head h of pool row 0) and krow() maps a key of this sequence
+  // to its pool row, one table lookup per lane and fetch (a 32-key tile may span two pages)
+  const long long seq0 = PAGED ? 0 : (long long)b * Tmax * H;
+  const bf16* kbase = (const bf16*)kcv + (seq0 + h) * HD;
+  const bf16* vbase = (const bf16*)vcv + (seq0 + h) * HD;
+  const uint8_t* k8base = (const uint8_t*)kcv + (seq0 + h) * HD;
+  const uint8_t* v8base = (const uint8_t*)vcv + (seq0 + h) * HD;
+  const long long sbase = seq0 + h;   // scale of key row k: sbase + k * H
   const long long ldkv = (long long)H * HD;
+  auto krow = [&](int k) __attribute__((always_inline)) -> long long {
+    if constexpr (PAGED) return kv_page_row(pg, b, k);
+    else return (long long)k;
+  };
   char* lv = smem + wave * VT;
   // V^T fragment reads (as attn_fwd3_k): rows 16 s + 4 hf + (i16 >> 2) [+ 8], d columns
   // 32 dt + 16 (g16 & 1) + 4 (i16 & 3); the swizzle ignores the row bits the 16 s / + 8 steps move
@@ -135,32 +149,33 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
   auto fetch = [&](int kt) __attribute__((always_inline)) {
     const int k0 = kt * kExtK;
     if constexpr (Q8) {
-      const int kr = min(k0 + r32, kmax);
-      const uint8_t* krow = k8base + (long long)kr * ldkv + 8 * hf;
+      const long long kr = krow(min(k0 + r32, kmax));
+      const uint8_t* kptr = k8base + kr * ldkv + 8 * hf;
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) kreg8[ks] = *reinterpret_cast<const u32x2*>(krow + 16 * ks);
-      ksreg = ksc[sbase + (long long)kr * H];
+      for (int ks = 0; ks < KS; ++ks) kreg8[ks] = *reinterpret_cast<const u32x2*>(kptr + 16 * ks);
+      ksreg = ksc[sbase + kr * H];
 #pragma unroll
       for (int i = 0; i < NVC; ++i) {
         const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
         u32x2 v = {0u, 0u};
         float sc = 0.f;                      // rows past kmax: code 0 x scale 0 = the staged zero
         if (k0 + r <= kmax) {
-          v = *reinterpret_cast<const u32x2*>(v8base + (long long)(k0 + r) * ldkv + ch * 8);
-          sc = vsc[sbase + (long long)(k0 + r) * H];
+          const long long vr = krow(k0 + r);
+          v = *reinterpret_cast<const u32x2*>(v8base + vr * ldkv + ch * 8);
+          sc = vsc[sbase + vr * H];
         }
         vreg8[i] = v;
         vsreg[i] = sc;
       }
     } else {
-      const bf16* krow = kbase + (long long)min(k0 + r32, kmax) * ldkv + 8 * hf;
+      const bf16* kptr = kbase + krow(min(k0 + r32, kmax)) * ldkv + 8 * hf;
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) kreg[ks] = *reinterpret_cast<const bf16x8*>(krow + 16 * ks);
+      for (int ks = 0; ks < KS; ++ks) kreg[ks] = *reinterpret_cast<const bf16x8*>(kptr + 16 * ks);
 #pragma unroll
       for (int i = 0; i < NVC; ++i) {
         const int c = l + 64 * i, r = c / CPR, ch = c % CPR;
         u32x4 v = {0u, 0u, 0u, 0u};
-        if (k0 + r <= kmax) v = *reinterpret_cast<const u32x4*>(vbase + (long long)(k0 + r) * ldkv + ch * 8);
+        if (k0 + r <= kmax) v = *reinterpret_cast<const u32x4*>(vbase + krow(k0 + r) * ldkv + ch * 8);
         vreg[i] = v;
       }
     }
@@ -299,11 +314,13 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
 
 // cache[b, len[b] + t, h, :] = the k / v parts of packed row b * T + t, for t < n[b] (n null: T)
 // and len[b] + t < Tmax.  One 16-byte vector per thread step.
+template <bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void kv_append_chunk_k(const bf16* __restrict__ ksrc, const bf16* __restrict__ vsrc,
                                                          long long ld, bf16* __restrict__ kc, bf16* __restrict__ vc,
                                                          const int* __restrict__ len_ptr, int len_rows,
                                                          const int* __restrict__ n_ptr, int B, int T, int H, int HD,
-                                                         int Tmax) {
+                                                         int Tmax, PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
   const int nv = H * HD / 8;               // 16-byte vectors per token row
   const long long per = (long long)B * T * nv;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * per;
@@ -318,8 +335,14 @@ __global__ __launch_bounds__(256) void kv_append_chunk_k(const bf16* __restrict_
     const int nb = n_ptr ? n_ptr[b] : T;
     if (len < 0 || t >= nb || len + t >= Tmax) continue;
     const bf16* src = (isv ? vsrc : ksrc) + row * ld + 8 * c;
-    bf16* dst = (isv ? vc : kc) + ((long long)b * Tmax + len + t) * H * HD + 8 * c;
-    *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+    if constexpr (PAGED) {   // an entry that maps no page: the append is dropped
+      bool mapped;
+      const long long prow = kv_page_row(pg, b, len + t, mapped);
+      if (mapped) *reinterpret_cast<u32x4*>((isv ? vc : kc) + prow * H * HD + 8 * c) = *reinterpret_cast<const u32x4*>(src);
+    } else {
+      bf16* dst = (isv ? vc : kc) + ((long long)b * Tmax + len + t) * H * HD + 8 * c;
+      *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+    }
   }
 }
 
@@ -369,4 +392,42 @@ extern "C" void dpfs_kv_append_chunk(const void* ksrc, const void* vsrc, long lo
   if (total > 0)
     kv_append_chunk_k<<<grid, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kc, (bf16*)vc, len,
                                            len_rows, n, B, T, H, HD, Tmax);
+}
+
+// ------------------------------------------------------------------------ paged KV cache --
+// The layout is in kv_page.h: kp / vp pools (P, PS, H, HD) of bf16, or with ks / vs non-null of
+// e4m3 codes with fp32 scale pools (P, PS, H); tbl (B, MP) device int32, PS = 1 << lg; len: B
+// device int32 (a paged cache is per-row); Tmax: the logical capacity of a sequence,
+// MP = ceil(Tmax / PS).  Grid and tiles are those of the contiguous form: the tiles are taken
+// over the logical key index.
+extern "C" void dpfs_attn_extend_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
+                                       const float* vs, const int* tbl, int MP, int P, int lg, const int* len,
+                                       const int* n, void* o, int B, int T, int H, int HD, int Tmax, float scale,
+                                       hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H);
+  const KvPageArgs<true> pg{tbl, MP, P, lg};
+#define EXT_LAUNCH(HD_, Q8_)                                                                                      \
+  attn_extend_k<HD_, Q8_, true><<<grid, 256, 0, s>>>((const bf16*)q, ldq, kp, vp, ks, vs, len, 1, n, (bf16*)o, T, H, \
+                                                     Tmax, scale, pg)
+  if (ks) {
+    if (HD == 32) EXT_LAUNCH(32, true);
+    else if (HD == 64) EXT_LAUNCH(64, true);
+    else EXT_LAUNCH(128, true);
+  } else {
+    if (HD == 32) EXT_LAUNCH(32, false);
+    else if (HD == 64) EXT_LAUNCH(64, false);
+    else EXT_LAUNCH(128, false);
+  }
+#undef EXT_LAUNCH
+}
+
+// dpfs_kv_append_chunk into bf16 pools (the fp8 form is dpfs_kv_append_chunk_q8_paged, kv8.hip).
+extern "C" void dpfs_kv_append_chunk_paged(const void* ksrc, const void* vsrc, long long ld, void* kp, void* vp,
+                                           const int* tbl, int MP, int P, int lg, const int* len, const int* n, int B,
+                                           int T, int H, int HD, int Tmax, hipStream_t s) {
+  const long long total = 2LL * B * T * (H * HD / 8);
+  const int grid = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  if (total > 0)
+    kv_append_chunk_k<true><<<grid, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (bf16*)kp, (bf16*)vp, len, 1,
+                                                 n, B, T, H, HD, Tmax, KvPageArgs<true>{tbl, MP, P, lg});
 }

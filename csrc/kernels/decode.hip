@@ -32,20 +32,28 @@
 // key's scale multiplies its finished dot product and the value's scale is folded into p in front
 // of the P.V FMAs (the row sum keeps the unscaled p): one multiply per key per side.  Grid,
 // splits, wave merge and partial format are those of the bf16 form.
+//
+// Paged KV cache (PAGED = true; the layout and its safety contract are in kv_page.h): kc / vc
+// (and ksc / vsc) are pools addressed through a block table instead of (b * Tmax + key); always
+// ROWS.  Splits, waves and the merge are taken over the logical key index as above, so a paged
+// launch computes, bit for bit, what the contiguous launch computes on the same cache content.
 #include "common.h"
 #include "kv8.h"
+#include "kv_page.h"
 #include "../dpfs_api.h"
 
 namespace dpfs {
 
 constexpr int kSplit = 256;   // keys per workgroup
 
-template <int HD, bool ROWS, bool Q8 = false>
+template <int HD, bool ROWS, bool Q8 = false, bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restrict__ q, long long ldq,
                                                           const void* __restrict__ kcv, const void* __restrict__ vcv,
                                                           const float* __restrict__ ksc, const float* __restrict__ vsc,
                                                           const int* __restrict__ len_ptr, int H, int Tmax,
-                                                          float scale, float* __restrict__ part) {
+                                                          float scale, float* __restrict__ part,
+                                                          PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
   const bf16* __restrict__ kc = (const bf16*)kcv;
   const bf16* __restrict__ vc = (const bf16*)vcv;
   const uint8_t* __restrict__ k8 = (const uint8_t*)kcv;
@@ -75,8 +83,16 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
   // scores: lane-per-key
   const int key = k0 + wave * 64 + l;
   float s = -INFINITY;
+  // PAGED: every lane looks up the pool row of its own key (a split covers whole pages); the P.V
+  // loop below takes the rows of its keys from the lanes that hold them
+  int prow = 0;
+  if constexpr (PAGED) {
+    if (key < L) prow = kv_page_row(pg, b, key);
+  }
   if (Q8 && key < L) {
-    const long long row = ((long long)b * Tmax + key) * H + h;
+    long long row;
+    if constexpr (PAGED) row = (long long)prow * H + h;
+    else row = ((long long)b * Tmax + key) * H + h;
     const uint8_t* krow = k8 + row * HD;
     float acc = 0.f;
 #pragma unroll
@@ -92,7 +108,9 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
     }
     s = acc * ksc[row];
   } else if (key < L) {
-    const bf16* krow = kc + (((long long)b * Tmax + key) * H + h) * HD;
+    const bf16* krow;
+    if constexpr (PAGED) krow = kc + ((long long)prow * H + h) * HD;
+    else krow = kc + (((long long)b * Tmax + key) * H + h) * HD;
     float acc = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
@@ -122,8 +140,12 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
   for (int i = 0; i < DG; ++i) {
     const int kk = kg + KG * i;             // key within the wave's 64
     const float pk = p_lds[wave][kk];
+    int pvrow = 0;
+    if constexpr (PAGED) pvrow = __shfl(prow, kk, 64);   // lane kk of this wave scored key kw0 + kk
     if (Q8 && kw0 + kk < L) {
-      const long long row = ((long long)b * Tmax + kw0 + kk) * H + h;
+      long long row;
+      if constexpr (PAGED) row = (long long)pvrow * H + h;
+      else row = ((long long)b * Tmax + kw0 + kk) * H + h;
       const uint8_t* vrow = v8 + row * HD + dg * DPL;
       const float pv = pk * vsc[row];
       uint32_t w[DPL / 4];
@@ -144,7 +166,9 @@ __global__ __launch_bounds__(256) void attn_decode_split_k(const bf16* __restric
         for (int j = 0; j < 4; ++j) o[4 * c + j] = fmaf(pv, v[j], o[4 * c + j]);
       }
     } else if (kw0 + kk < L) {
-      const bf16* vrow = vc + (((long long)b * Tmax + kw0 + kk) * H + h) * HD + dg * DPL;
+      const bf16* vrow;
+      if constexpr (PAGED) vrow = vc + ((long long)pvrow * H + h) * HD + dg * DPL;
+      else vrow = vc + (((long long)b * Tmax + kw0 + kk) * H + h) * HD + dg * DPL;
 #pragma unroll
       for (int c = 0; c < DPL / 8; ++c) {
         float v[8];
@@ -319,12 +343,14 @@ __global__ __launch_bounds__(64 * KS) void gemv16_k(const bf16* __restrict__ A, 
 // the rotated k row and the v row at row *len (ROWS: len[b]): one launch instead of rope_k +
 // kv_append_k.  Same arithmetic and rounding as rope_vec_k (sign +1).  8 frequency pairs per
 // thread.
-template <bool ROWS>
+template <bool ROWS, bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, long long ld,
                                                      const int64_t* __restrict__ pos,
                                                      const float* __restrict__ tab, bf16* __restrict__ kc,
                                                      bf16* __restrict__ vc, const int* __restrict__ len_ptr,
-                                                     int B, int H, int HD, int Tmax) {
+                                                     int B, int H, int HD, int Tmax, PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
+  static_assert(ROWS || !PAGED, "a paged cache is per-row");
   const int t0 = ROWS ? 0 : *len_ptr;
   const bool app0 = ROWS || (t0 >= 0 && t0 < Tmax);   // full cache: rotate, append nothing
   const int h2 = HD / 2, q8 = h2 / 8;
@@ -354,7 +380,17 @@ __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, lon
       }
       *reinterpret_cast<bf16x8*>(base + f0) = oa;
       *reinterpret_cast<bf16x8*>(base + h2 + f0) = ob;
-      if (head >= H && app) {
+      if constexpr (PAGED) {
+        if (head >= H && app) {   // an entry that maps no page: the append is dropped
+          bool mapped;
+          const long long prow = kv_page_row(pg, b, t, mapped);
+          bf16* dst = kc + (prow * H + (head - H)) * HD;
+          if (mapped) {
+            *reinterpret_cast<bf16x8*>(dst + f0) = oa;
+            *reinterpret_cast<bf16x8*>(dst + h2 + f0) = ob;
+          }
+        }
+      } else if (head >= H && app) {
         bf16* dst = kc + (((long long)b * Tmax + t) * H + (head - H)) * HD;
         *reinterpret_cast<bf16x8*>(dst + f0) = oa;
         *reinterpret_cast<bf16x8*>(dst + h2 + f0) = ob;
@@ -364,8 +400,14 @@ __global__ __launch_bounds__(256) void rope_append_k(bf16* __restrict__ qkv, lon
       const int t = ROWS ? len_ptr[b] : t0;
       if (ROWS && (t < 0 || t >= Tmax)) continue;   // this row is full
       const bf16* src = qkv + (long long)b * ld + 2 * H * HD + 8 * c;
-      bf16* dst = vc + ((long long)b * Tmax + t) * H * HD + 8 * c;
-      *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+      if constexpr (PAGED) {
+        bool mapped;
+        const long long prow = kv_page_row(pg, b, t, mapped);
+        if (mapped) *reinterpret_cast<u32x4*>(vc + prow * H * HD + 8 * c) = *reinterpret_cast<const u32x4*>(src);
+      } else {
+        bf16* dst = vc + ((long long)b * Tmax + t) * H * HD + 8 * c;
+        *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+      }
     }
   }
 }
@@ -508,4 +550,44 @@ extern "C" void dpfs_rope_append_rows(void* qkv, long long ld, const int64_t* po
   const int total = B * 2 * H * (HD / 16) + B * H * HD / 8;
   const int grid = (total + 255) / 256;
   rope_append_k<true><<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (bf16*)kc, (bf16*)vc, len, B, H, HD, Tmax);
+}
+
+// ------------------------------------------------------------------------ paged KV cache --
+// The layout is in kv_page.h: kp / vp pools (P, PS, H, HD) of bf16, or with ks / vs non-null of
+// e4m3 codes with fp32 scale pools (P, PS, H); tbl (B, MP) device int32, PS = 1 << lg; len: B
+// device int32 (a paged cache is per-row); Tmax: the logical capacity of a sequence,
+// MP = ceil(Tmax / PS).  Grid, splits and the combine launch are those of the contiguous form at
+// the same Tmax.
+extern "C" void dpfs_attn_decode_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
+                                       const float* vs, const int* tbl, int MP, int P, int lg, const int* len, void* o,
+                                       long long ldo, float* part, int B, int H, int HD, int Tmax, float scale,
+                                       hipStream_t s) {
+  const int ns = dpfs_decode_nsplit(Tmax);
+  const KvPageArgs<true> pg{tbl, MP, P, lg};
+#define DEC_PAGED(HD_, Q8_)                                                                                          \
+  do {                                                                                                               \
+    attn_decode_split_k<HD_, true, Q8_, true><<<dim3(ns, B * H), 256, 0, s>>>((const bf16*)q, ldq, kp, vp, ks, vs, len, \
+                                                                               H, Tmax, scale, part, pg);           \
+    attn_decode_combine_k<HD_, true><<<B * H, 64, 0, s>>>(part, ns, len, (bf16*)o, ldo, H);                          \
+  } while (0)
+  if (ks) {
+    if (HD == 32) DEC_PAGED(32, true);
+    else if (HD == 64) DEC_PAGED(64, true);
+    else DEC_PAGED(128, true);
+  } else {
+    if (HD == 32) DEC_PAGED(32, false);
+    else if (HD == 64) DEC_PAGED(64, false);
+    else DEC_PAGED(128, false);
+  }
+#undef DEC_PAGED
+}
+
+// rope_append_rows into bf16 pools (the fp8 form is dpfs_rope_append_q8_paged, kv8.hip).
+extern "C" void dpfs_rope_append_paged(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kp, void* vp,
+                                       const int* tbl, int MP, int P, int lg, const int* len, int B, int H, int HD,
+                                       int Tmax, hipStream_t s) {
+  const int total = B * 2 * H * (HD / 16) + B * H * HD / 8;
+  const int grid = (total + 255) / 256;
+  rope_append_k<true, true><<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (bf16*)kp, (bf16*)vp, len, B, H, HD, Tmax,
+                                                 KvPageArgs<true>{tbl, MP, P, lg});
 }

@@ -15,19 +15,24 @@
 // end of the index space: every index space below is a whole number of groups, groups start at
 // multiples of their size, and the sizes divide 64.  Rows that are not written still take part in
 // the exchange (on zeros) so that no lane of a group leaves it early.
+//
+// Paged KV cache (PAGED = true; kv_page.h): k8 / v8 / ks / vs are pools and the written row is the
+// one the block table gives (b, len[b] + t); an entry that maps no page drops the write.
 #include "kv8.h"
+#include "kv_page.h"
 #include "../dpfs_api.h"
 
 namespace dpfs {
 
-template <int HD>
+template <int HD, bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void kv_append_chunk_q8_k(const bf16* __restrict__ ksrc,
                                                             const bf16* __restrict__ vsrc, long long ld,
                                                             uint8_t* __restrict__ k8, uint8_t* __restrict__ v8,
                                                             float* __restrict__ ks, float* __restrict__ vs,
                                                             const int* __restrict__ len_ptr, int len_rows,
                                                             const int* __restrict__ n_ptr, int B, int T, int H,
-                                                            int Tmax) {
+                                                            int Tmax, PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
   constexpr int G = HD / 8;                  // lanes per row, 8 values (16 bytes in, 8 out) each
   const long long per = (long long)B * T * H * G;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * per;
@@ -46,7 +51,16 @@ __global__ __launch_bounds__(256) void kv_append_chunk_q8_k(const bf16* __restri
     bf16x8 x = {};
     if (live) x = *reinterpret_cast<const bf16x8*>((isv ? vsrc : ksrc) + row * ld + (long long)h * HD + 8 * c);
     const float scale = kv8_scale(kv8_group_max<G>(kv8_amax8(x, 0.f)));
-    if (live) {
+    if constexpr (PAGED) {
+      if (live) {   // an entry that maps no page: the append is dropped, codes and scale
+        bool mapped;
+        const long long crow = (long long)kv_page_row(pg, b, len + t, mapped) * H + h;
+        if (mapped) {
+          *reinterpret_cast<u32x2*>((isv ? v8 : k8) + crow * HD + 8 * c) = kv8_enc8(x, scale);
+          if (c == 0) (isv ? vs : ks)[crow] = 1.f / scale;
+        }
+      }
+    } else if (live) {
       const long long crow = ((long long)b * Tmax + len + t) * H + h;
       *reinterpret_cast<u32x2*>((isv ? v8 : k8) + crow * HD + 8 * c) = kv8_enc8(x, scale);
       if (c == 0) (isv ? vs : ks)[crow] = 1.f / scale;
@@ -57,13 +71,15 @@ __global__ __launch_bounds__(256) void kv_append_chunk_q8_k(const bf16* __restri
 // Same index space, arithmetic and bf16 rounding as rope_append_k (8 frequency pairs per thread
 // for the q and k heads, then one 16-byte vector of v per thread); a rotated k head is the
 // HD / 16 consecutive threads of its pairs.
-template <int HD, bool ROWS>
+template <int HD, bool ROWS, bool PAGED = false, typename... PG>
 __global__ __launch_bounds__(256) void rope_append_q8_k(bf16* __restrict__ qkv, long long ld,
                                                         const int64_t* __restrict__ pos,
                                                         const float* __restrict__ tab, uint8_t* __restrict__ k8,
                                                         uint8_t* __restrict__ v8, float* __restrict__ ks,
                                                         float* __restrict__ vs, const int* __restrict__ len_ptr,
-                                                        int B, int H, int Tmax) {
+                                                        int B, int H, int Tmax, PG... pgv) {
+  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
+  static_assert(ROWS || !PAGED, "a paged cache is per-row");
   constexpr int h2 = HD / 2, q8 = h2 / 8, G = HD / 8;
   const int t0 = ROWS ? 0 : *len_ptr;
   const bool app0 = ROWS || (t0 >= 0 && t0 < Tmax);   // full cache: rotate, append nothing
@@ -95,7 +111,18 @@ __global__ __launch_bounds__(256) void rope_append_q8_k(bf16* __restrict__ qkv, 
       *reinterpret_cast<bf16x8*>(base + h2 + f0) = ob;
       // the head's amax over its q8 threads (the q heads take part: their groups are whole too)
       const float scale = kv8_scale(kv8_group_max<q8>(kv8_amax8(ob, kv8_amax8(oa, 0.f))));
-      if (head >= H && app) {
+      if constexpr (PAGED) {
+        if (head >= H && app) {   // an entry that maps no page: the append is dropped
+          bool mapped;
+          const long long crow = (long long)kv_page_row(pg, b, t, mapped) * H + (head - H);
+          uint8_t* dst = k8 + crow * HD;
+          if (mapped) {
+            *reinterpret_cast<u32x2*>(dst + f0) = kv8_enc8(oa, scale);
+            *reinterpret_cast<u32x2*>(dst + h2 + f0) = kv8_enc8(ob, scale);
+            if (f0 == 0) ks[crow] = 1.f / scale;
+          }
+        }
+      } else if (head >= H && app) {
         const long long crow = ((long long)b * Tmax + t) * H + (head - H);
         uint8_t* dst = k8 + crow * HD;
         *reinterpret_cast<u32x2*>(dst + f0) = kv8_enc8(oa, scale);
@@ -109,7 +136,16 @@ __global__ __launch_bounds__(256) void rope_append_q8_k(bf16* __restrict__ qkv, 
       const bool app = !ROWS || (t >= 0 && t < Tmax);   // ROWS: this row may be full
       const bf16x8 x = *reinterpret_cast<const bf16x8*>(qkv + (long long)b * ld + 2 * H * HD + h * HD + 8 * c);
       const float scale = kv8_scale(kv8_group_max<G>(kv8_amax8(x, 0.f)));
-      if (app) {
+      if constexpr (PAGED) {
+        if (app) {
+          bool mapped;
+          const long long crow = (long long)kv_page_row(pg, b, t, mapped) * H + h;
+          if (mapped) {
+            *reinterpret_cast<u32x2*>(v8 + crow * HD + 8 * c) = kv8_enc8(x, scale);
+            if (c == 0) vs[crow] = 1.f / scale;
+          }
+        }
+      } else if (app) {
         const long long crow = ((long long)b * Tmax + t) * H + h;
         *reinterpret_cast<u32x2*>(v8 + crow * HD + 8 * c) = kv8_enc8(x, scale);
         if (c == 0) vs[crow] = 1.f / scale;
@@ -159,5 +195,41 @@ extern "C" void dpfs_rope_append_q8(void* qkv, long long ld, const int64_t* pos,
     else if (HD == 64) Q8_LAUNCH(64, false);
     else Q8_LAUNCH(128, false);
   }
+#undef Q8_LAUNCH
+}
+
+// ------------------------------------------------------------------------ paged KV cache --
+// The quantising appends into fp8 pools (the layout is in kv_page.h): kp / vp (P, PS, H, HD) e4m3
+// codes, ks / vs (P, PS, H) fp32 scales, tbl (B, MP) device int32, PS = 1 << lg; len: B device
+// int32 (a paged cache is per-row); Tmax: the logical capacity of a sequence.
+extern "C" void dpfs_kv_append_chunk_q8_paged(const void* ksrc, const void* vsrc, long long ld, void* kp, void* vp,
+                                              float* ks, float* vs, const int* tbl, int MP, int P, int lg,
+                                              const int* len, const int* n, int B, int T, int H, int HD, int Tmax,
+                                              hipStream_t s) {
+  const long long total = 2LL * B * T * H * (HD / 8);
+  const int grid = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  if (total <= 0) return;
+  const KvPageArgs<true> pg{tbl, MP, P, lg};
+#define Q8_LAUNCH(HD_)                                                                                          \
+  kv_append_chunk_q8_k<HD_, true><<<grid, 256, 0, s>>>((const bf16*)ksrc, (const bf16*)vsrc, ld, (uint8_t*)kp, \
+                                                       (uint8_t*)vp, ks, vs, len, 1, n, B, T, H, Tmax, pg)
+  if (HD == 32) Q8_LAUNCH(32);
+  else if (HD == 64) Q8_LAUNCH(64);
+  else Q8_LAUNCH(128);
+#undef Q8_LAUNCH
+}
+
+extern "C" void dpfs_rope_append_q8_paged(void* qkv, long long ld, const int64_t* pos, const float* tab, void* kp,
+                                          void* vp, float* ks, float* vs, const int* tbl, int MP, int P, int lg,
+                                          const int* len, int B, int H, int HD, int Tmax, hipStream_t s) {
+  const int total = B * 2 * H * (HD / 16) + B * H * (HD / 8);
+  const int grid = (total + 255) / 256;
+  const KvPageArgs<true> pg{tbl, MP, P, lg};
+#define Q8_LAUNCH(HD_)                                                                                            \
+  rope_append_q8_k<HD_, true, true><<<grid, 256, 0, s>>>((bf16*)qkv, ld, pos, tab, (uint8_t*)kp, (uint8_t*)vp, ks, vs, \
+                                                         len, B, H, Tmax, pg)
+  if (HD == 32) Q8_LAUNCH(32);
+  else if (HD == 64) Q8_LAUNCH(64);
+  else Q8_LAUNCH(128);
 #undef Q8_LAUNCH
 }

@@ -93,6 +93,10 @@ def get_test_args(argv=None):
                    help="prefill a prompt in pieces of at most this many tokens (0: whole)")
     g.add_argument("--kv_cache_dtype", choices=["act", "fp8"], default="act",
                    help="KV cache storage: the activation dtype, or e4m3 codes with per-row fp32 scales")
+    g.add_argument("--kv_page", type=int, default=0,
+                   help="keep the KV cache in pages of this many tokens (a power of two in [16, 256]; 0: contiguous)")
+    g.add_argument("--kv_pool_pages", type=int, default=0,
+                   help="pages per pool of the paged KV cache (0: batch * ceil(t_max / kv_page), which cannot run out)")
     g = p.add_argument_group("other")
     g.add_argument("--random_seed", type=int, default=0)
     g.add_argument("--device", type=str, default=None)
@@ -118,7 +122,7 @@ def calc_loss(model: Transformer, dataloader, dev) -> float:
 def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True,
                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                   prefill_chunk: int = 0, kv_dtype=None, repetition_penalty=1.0, presence_penalty=0.0,
-                  frequency_penalty=0.0, return_logprobs: bool = False):
+                  frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
@@ -129,7 +133,8 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
     in pieces of at most that many tokens (KV-cached decoding only); ``kv_dtype`` "fp8" keeps the
     KV cache as e4m3 codes (``generate``).  The three penalties are ``generate``'s (KV-cached
     decoding only); ``return_logprobs`` returns (ids, the model's log-probability of every
-    generated id, a final EOS included) instead of the ids."""
+    generated id, a final EOS included) instead of the ids.  ``kv_page`` / ``kv_pool_pages`` page
+    the KV cache (``generate``; KV-cached decoding only)."""
     pen = (repetition_penalty, presence_penalty, frequency_penalty) != (1.0, 0.0, 0.0) or return_logprobs
     if not kv_cache and (temperature != 0 or isinstance(seed, (list, tuple, torch.Tensor)) or pen):
         raise ValueError("sampling (--temperature > 0), penalties and log-probabilities run in the KV-cached decode "
@@ -141,7 +146,8 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
         out = generate(model, tokens, max_new_tokens=max(1, max_len + 1 - n0), eos_id=eos, temperature=temperature,
                        top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype,
                        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                       frequency_penalty=frequency_penalty, return_logprobs=return_logprobs)
+                       frequency_penalty=frequency_penalty, return_logprobs=return_logprobs, kv_page=kv_page,
+                       kv_pool_pages=kv_pool_pages)
         out, lps = (out[0][0], out[1][0]) if return_logprobs else (out[0], None)
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
@@ -164,7 +170,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
 def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
                         top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None,
                         repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        return_logprobs: bool = False):
+                        return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None):
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
@@ -182,7 +188,7 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
         row = lambda v, b: [v[b]] if seq(v) else v                # a prompt's own value, still per row
         return [greedy_decode(model, p, bos, eos, max_len, dev, True, row(temperature, b), row(top_k, b),
                               row(top_p, b), row(seed, b), prefill_chunk, kv_dtype, repetition_penalty,
-                              presence_penalty, frequency_penalty, return_logprobs)
+                              presence_penalty, frequency_penalty, return_logprobs, kv_page, kv_pool_pages)
                 for b, p in enumerate(prompts)]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
@@ -191,7 +197,7 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, prompt_lens=lens,
                     prefill_chunk=prefill_chunk, kv_dtype=kv_dtype, repetition_penalty=repetition_penalty,
                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                    return_logprobs=return_logprobs)
+                    return_logprobs=return_logprobs, kv_page=kv_page, kv_pool_pages=kv_pool_pages)
     outs, lps = outs if return_logprobs else (outs, [None] * len(prompts))
     res = []
     for p, out, lp in zip(prompts, outs, lps):
@@ -266,6 +272,8 @@ def test(rank, args):
         sampling.update(pens)
     if args.logprobs:
         sampling["return_logprobs"] = True
+    if args.kv_page:
+        sampling.update(kv_page=args.kv_page, kv_pool_pages=args.kv_pool_pages or None)
     split = lambda outs: zip(*outs) if args.logprobs else (outs, [None] * len(outs))
     decoded = []
     if args.synthetic_prompts or not args.tokenizer_path:
@@ -299,6 +307,20 @@ def test(rank, args):
     return results
 
 
+def check_kv_page_args(args) -> None:
+    """--kv_page / --kv_pool_pages: the page size is ``generate``'s (a power of two in [16, 256]), and
+    a paged cache is a KV cache."""
+    if args.kv_page < 0 or args.kv_pool_pages < 0:
+        raise ValueError("--kv_page and --kv_pool_pages must be >= 0")
+    if args.kv_page == 0 and args.kv_pool_pages > 0:
+        raise ValueError("--kv_pool_pages sizes the pools of a paged KV cache: give --kv_page too")
+    if args.kv_page > 0:
+        if args.no_kv_cache:
+            raise ValueError("--kv_page pages the KV cache: drop --no_kv_cache")
+        if args.kv_page < 16 or args.kv_page > 256 or args.kv_page & (args.kv_page - 1):
+            raise ValueError(f"--kv_page must be a power of two in [16, 256], got {args.kv_page}")
+
+
 def main(argv=None):
     args = get_test_args(argv)
     if args.no_kv_cache and (args.temperature != 0 or args.per_prompt_seed):
@@ -313,6 +335,7 @@ def main(argv=None):
         raise ValueError("--prefill_chunk must be >= 0, and > 0 chunks the KV-cached prefill: drop --no_kv_cache")
     if args.kv_cache_dtype != "act" and args.no_kv_cache:
         raise ValueError("--kv_cache_dtype chooses the storage of the KV cache: drop --no_kv_cache")
+    check_kv_page_args(args)
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)
     mp.spawn(test, args=(args,), nprocs=args.tp_size, join=True)

@@ -48,6 +48,14 @@ directly by the fp8 forms of the attention kernels (``_attn_decode_q8``, ``_attn
 only storage is fp8, the math stays fp32 / bf16.  The whole-prompt prefill attends its own fresh,
 unquantised q / k / v; everything that reads the cache later sees the quantised rows.
 
+Paged KV cache (``kv_page=N``; the default 0 is the contiguous slab above): ``PagedKVCache`` keeps
+per layer and side one pool ``(P, N, H_local, hd)`` and one block table ``tbl`` int32 ``(B, MP)``
+for all layers (csrc/kernels/kv_page.h is the layout), always with per-row lengths.  The host maps
+pages from a free list in front of every prefill piece, decode step or graph replay
+(``reserve``); the kernels (the ``_paged`` ops: the PAGED forms of the same kernels) read the
+table from device memory and are safe for any table content, so the mapping is device data like
+the lengths and a session's graphs are captured once.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -78,6 +86,8 @@ class KVCache:
     """Per-layer key/value buffers ``(B, T_max, H_local, hd)`` in the activation dtype
     (``kv_dtype`` None), or with ``kv_dtype="fp8"`` as ``torch.float8_e4m3fn`` codes plus the fp32
     row scales ``ks`` / ``vs`` ``(B, T_max, H_local)`` (head_dim 32, 64 or 128)."""
+
+    page = 0    # the page size of a ``PagedKVCache``; 0: this contiguous form
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
                  ragged: bool = False, kv_dtype: Optional[str] = None):
@@ -157,6 +167,117 @@ class KVCache:
         if self.ragged:
             return self.len_t.clamp(max=self.t_max - 1).long()
         return self.len_t.long().expand(B).contiguous()
+
+
+def _check_kv_page(page: int, who: str = "generate") -> int:
+    if not isinstance(page, int) or page < 16 or page > 256 or page & (page - 1):
+        raise ValueError(f"{who}: kv_page must be a power of two in [16, 256] (0: no paging), got {page!r}")
+    return page
+
+
+class PagedKVCache(KVCache):
+    """The paged form of ``KVCache`` (csrc/kernels/kv_page.h is the layout): per layer and side one
+    pool ``(P, page, H_local, hd)`` of ``P = pool_pages`` pages (``kv_dtype="fp8"``: e4m3 codes plus
+    fp32 scale pools ``(P, page, H_local)``), and one block table ``tbl`` int32 ``(B, MP)``,
+    ``MP = ceil(t_max / page)``, for all layers: key t of row b lives in pool row
+    ``tbl[b, t // page] * page + t % page``; -1 maps nothing.  Always per-row (``ragged``).
+
+    The pages are handed out on the host: ``reserve(need)`` maps pages from the free list until
+    row b can hold ``need[b]`` tokens and uploads the table when it changed; the kernels read the
+    table from device memory, so captured graphs stay valid as the mapping changes.  The default
+    ``pool_pages = B * MP`` can never run out; a smaller pool serves batches whose rows do not all
+    reach ``t_max``, and ``reserve`` raises ``RuntimeError`` on the host when it cannot cover a
+    request.  ``page_order`` (a permutation of ``range(P)``, or a callable ``P -> permutation``)
+    is the order in which the free list hands pages out (tests: non-contiguous, interleaved)."""
+
+    def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device, page: int,
+                 pool_pages: Optional[int] = None, kv_dtype: Optional[str] = None, page_order=None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"PagedKVCache: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
+        self.page = _check_kv_page(page, "PagedKVCache")
+        device = torch.device(device)
+        if hd not in (32, 64, 128) and (kv_dtype == "fp8" or device.type == "cuda"):
+            raise ValueError(f"PagedKVCache: the paged kernels need head_dim 32, 64 or 128, got {hd}")
+        self.kv_dtype = kv_dtype
+        self.B = B
+        self.t_max = t_max
+        self.max_pages = -(-t_max // page)             # MP: table columns
+        P = B * self.max_pages if pool_pages is None else int(pool_pages)
+        if P < 1 or P * page >= 2 ** 31:
+            raise ValueError(f"PagedKVCache: pool_pages must be >= 1 with pool_pages * page < 2^31, got {P}")
+        self.pool_pages = P
+        if kv_dtype == "fp8":
+            dtype = torch.float8_e4m3fn
+            self.ks = [torch.empty(P, page, h_local, dtype=torch.float32, device=device) for _ in range(n_layers)]
+            self.vs = [torch.empty(P, page, h_local, dtype=torch.float32, device=device) for _ in range(n_layers)]
+        self.k = [torch.empty(P, page, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.v = [torch.empty(P, page, h_local, hd, dtype=dtype, device=device) for _ in range(n_layers)]
+        order = list(page_order(P) if callable(page_order) else range(P) if page_order is None else page_order)
+        if sorted(order) != list(range(P)):
+            raise ValueError(f"PagedKVCache: page_order must be a permutation of range({P})")
+        self._order = order
+        self.tbl = torch.full((B, self.max_pages), -1, dtype=torch.int32, device=device)
+        self.tbl_host = torch.full((B, self.max_pages), -1, dtype=torch.int32)     # the host mirror
+        self.free = list(reversed(order))          # the free list: pages are popped from its end
+        self.mapped = [0] * B                      # pages mapped per row
+        self.uploads = 0                           # table uploads so far
+        self.len = 0
+        self.len_t = torch.zeros(B, dtype=torch.int32, device=device)
+        self.lens = [0] * B
+        self._sample_rows = None
+        self._sample_pen = None
+
+    def tensors(self):
+        """Every device buffer of the cache: the pools (fp8: codes and scales) and the table."""
+        return super().tensors() + [self.tbl]
+
+    def scales(self, li: int):
+        """The (ks, vs) scale pools of layer ``li``, (None, None) for bf16 pools: the two
+        arguments by which the paged ops tell the two forms apart."""
+        return (self.ks[li], self.vs[li]) if self.fp8 else (None, None)
+
+    def sample_rows(self) -> "SampleRows":
+        if self._sample_rows is None:
+            self._sample_rows = SampleRows(self.B, self.len_t.device)
+        return self._sample_rows
+
+    def sample_pen(self, vocab: int) -> "SamplePen":
+        if self._sample_pen is None or self._sample_pen.vocab != vocab:
+            self._sample_pen = SamplePen(self.B, vocab, self.len_t.device)
+        return self._sample_pen
+
+    def _upload(self):
+        self.tbl.copy_(self.tbl_host)
+        self.uploads += 1
+
+    def reserve(self, need) -> None:
+        """Map pages until row b can hold ``need[b]`` tokens (clamped at ``t_max``); one table
+        upload, and only if a page was mapped.  Raises ``RuntimeError`` before anything is mapped
+        when the free list cannot cover the request."""
+        want = [-(-min(max(int(n), 0), self.t_max) // self.page) for n in need]
+        if len(want) != self.B:
+            raise ValueError(f"PagedKVCache.reserve: need one token count per row ({self.B}), got {len(want)}")
+        extra = sum(max(w - m, 0) for w, m in zip(want, self.mapped))
+        if extra == 0:
+            return
+        if extra > len(self.free):
+            raise RuntimeError(f"PagedKVCache.reserve: {extra} pages wanted, {len(self.free)} free (a pool of "
+                               f"{self.pool_pages} pages of {self.page} tokens; rows hold {self.mapped} pages and "
+                               f"need {want})")
+        for b, w in enumerate(want):
+            while self.mapped[b] < w:
+                self.tbl_host[b, self.mapped[b]] = self.free.pop()
+                self.mapped[b] += 1
+        self._upload()
+
+    def reset(self):
+        """Return every page to the free list (in its original order) and unmap the table."""
+        super().reset()
+        if any(self.mapped):
+            self.free = list(reversed(self._order))
+            self.mapped = [0] * self.B
+            self.tbl_host.fill_(-1)
+            self._upload()
 
 
 class SampleRows:
@@ -312,7 +433,20 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
     k_ = K(qkv)
     k_.rope_(qkv, positions, tab, 2 * h, hd, False)
     scale = 1.0 / math.sqrt(hd)
-    if cache.len == 0:
+    if cache.page:
+        # paged cache: the appends and the extend attention go through the block table; the
+        # whole-prompt prefill fills the pages at device length 0 (the real ids of every row:
+        # ``n_t``) and still attends its fresh q / k / v
+        pools = (cache.k[li], cache.v[li], *cache.scales(li), cache.tbl, cache.len_t)
+        k_._kv_append_chunk_paged(qkv, *pools, n_t, cache.t_max, cache.page)
+        if cache.len == 0:
+            q = qkv[:, : h * hd].view(B, T, h, hd)
+            kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
+            v = qkv[:, 2 * h * hd:].view(B, T, h, hd)
+            o, _ = k_.attn_fwd(q, kk, v, scale, True)
+        else:
+            o = k_._attn_extend_paged(qkv, *pools, n_t, cache.t_max, cache.page, scale)
+    elif cache.len == 0:
         # prefill: causal flash attention over the prompt
         q = qkv[:, : h * hd].view(B, T, h, hd)
         kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
@@ -340,14 +474,18 @@ def _prefill_piece(model, ids: torch.Tensor, cache: KVCache, n: Optional[List[in
     hidden states (B, T, D) in front of the final norm."""
     B, T = ids.shape
     dev = ids.device
+    if cache.page:      # pages for what this piece appends, before anything is launched
+        cache.reserve(c + m for c, m in zip(cache.lens, n if n is not None else [T] * B))
     dt = model.act_dtype(dev)
     model.embedding.out_dtype = dt
     x = model.embedding(ids).reshape(B * T, -1).to(dt)
     n_t = None
     if cache.len == 0:
         positions = torch.arange(T, device=dev).repeat(B)
-        if cache.fp8:
-            cache.sync_device_len()       # the quantising append of the prefill reads len_t (0)
+        if cache.fp8 or cache.page:
+            cache.sync_device_len()       # the quantising / paged append of the prefill reads len_t (0)
+        if cache.page and n is not None:  # a paged prefill appends the real ids only (pages are per need)
+            n_t = torch.tensor(n, dtype=torch.int32, device=dev)
     else:
         cache.sync_device_len()
         base = cache.lens if cache.ragged else [cache.len] * B
@@ -407,6 +545,8 @@ def logits_step(model, ids: torch.Tensor, cache: KVCache, lens=None, prefill_chu
     else:
         assert cache.len + T <= cache.t_max <= model.args.maxlen
     if T == 1 and cache.len > 0:
+        if cache.page:
+            cache.reserve(m + 1 for m in cache.lens)
         cache.sync_device_len()
         pos = cache.device_pos() if cache.ragged else torch.full((B,), cache.len, dtype=torch.int64, device=dev)
         _, logits = decode_step(model, ids, pos, cache)
@@ -480,7 +620,11 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
         else:
             x, h1, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, L.s1, L.eps1)
         qkv = proj(h1, W(L.wqkv), L.bqkv)
-        if cache.fp8:   # head_dim 32 / 64 / 128: always the fused kernel
+        if cache.page:  # through the block table; head_dim 32 / 64 / 128: always the fused kernel
+            pools = (cache.k[li], cache.v[li], *cache.scales(li), cache.tbl, cache.len_t, cache.t_max, cache.page)
+            k._rope_append_paged(qkv, pos, tab, *pools)
+            o = k._attn_decode_paged(qkv, *pools, 1.0 / math.sqrt(L.hd))
+        elif cache.fp8:   # head_dim 32 / 64 / 128: always the fused kernel
             k._rope_append_q8(qkv, pos, tab, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t)
             o = k._attn_decode_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t,
                                   1.0 / math.sqrt(L.hd))
@@ -524,7 +668,11 @@ def _decode_step_modules(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVC
         qkv = attn.wqkv(layer.norm1(x))                      # (B, 3*h*hd)
         k_ = K(qkv)
         k_.rope_(qkv, pos, tab, 2 * h, hd, False)
-        if cache.fp8:   # the un-fused single-token append: the chunk kernel at T = 1
+        if cache.page:  # the un-fused single-token append: the paged chunk kernel at T = 1
+            pools = (cache.k[li], cache.v[li], *cache.scales(li), cache.tbl, cache.len_t)
+            k_._kv_append_chunk_paged(qkv, *pools, None, cache.t_max, cache.page)
+            o = k_._attn_decode_paged(qkv, *pools, cache.t_max, cache.page, 1.0 / math.sqrt(hd))
+        elif cache.fp8:   # the un-fused single-token append: the chunk kernel at T = 1
             k_._kv_append_chunk_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, None)
             o = k_._attn_decode_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t,
                                    1.0 / math.sqrt(hd))
@@ -622,33 +770,42 @@ def _use_graph(dev) -> bool:
             and (p is None or p.tp_size == 1))
 
 
-_SESSIONS = {}   # (id(model), B, t_max, device, kv_dtype, ragged) -> KV cache + captured decode graphs
+_SESSIONS = {}   # (id(model), B, t_max, device, kv_dtype, ragged[, kv_page, kv_pool_pages]) -> KV cache + decode graphs
 
 
-def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Optional[str] = None):
+def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Optional[str] = None,
+             kv_page: int = 0, kv_pool_pages: Optional[int] = None):
     """The KV cache and decode graphs for this (model, batch, length, cache dtype, uniform /
-    ragged): reused
+    ragged, page size, pool pages): reused
     by the next generate() call of the same shape, so serving pays the graph capture once (a
     ragged session serves every mix of prompt lengths: they are device data).  Reused only
     while it is the same live model object and no parameter changed since the capture (the
     graphs hold the bf16 weight copies of that version); otherwise rebuilt.  One kept shape
     per model (with a session per cache dtype of that shape), and only caches up to
-    DPFS_DECODE_SESSION_MAX_GB (default 16; an fp8 cache counts codes and scales) are kept;
-    ``clear_sessions()`` frees them."""
+    DPFS_DECODE_SESSION_MAX_GB (default 16; an fp8 cache counts codes and scales, a paged one its
+    pools and table) are kept; ``clear_sessions()`` frees them.  A paged cache (``kv_page`` > 0) is
+    a form of the cache like its dtype: its key is the unpaged key followed by (kv_page,
+    kv_pool_pages), and the paged sessions of the kept shape stay beside the unpaged ones."""
     attn0 = model.layers[0].attn
     key = (id(model), B, t_max, str(dev), kv_dtype, ragged)
+    if kv_page:
+        key += (kv_page, kv_pool_pages)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
         ent["cache"].reset()
         return ent["cache"], ent["graphs"]
-    cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev,
-                    ragged, kv_dtype)
+    if kv_page:
+        cache = PagedKVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev),
+                             dev, kv_page, kv_pool_pages, kv_dtype)
+    else:
+        cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev,
+                        ragged, kv_dtype)
     graphs = {}
-    kv_bytes = cache.nbytes()             # the fp8 form: codes and scales
+    kv_bytes = cache.nbytes()             # the fp8 form: codes and scales; the paged form: pools and table
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
     if _use_graph(dev) and kv_bytes <= keep_gb * 2 ** 30:
-        shape = lambda k: k[:4] + k[5:]
+        shape = lambda k: k[:4] + k[5:6]      # (what the cache holds, not how: dtype and paging aside)
         for k in [k for k, e in _SESSIONS.items()
                   if e["model"]() is None or (k[0] == id(model) and shape(k) != shape(key))]:
             del _SESSIONS[k]          # dead models, and other shapes of this one (its other cache dtype stays)
@@ -679,7 +836,8 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
              max_len: Optional[int] = None, temperature=0.0, top_k=0, top_p=1.0,
              seed=0, prompt_lens=None, prefill_chunk: int = 0,
              kv_dtype: Optional[str] = None, repetition_penalty=1.0, presence_penalty=0.0,
-             frequency_penalty=0.0, return_logprobs: bool = False):
+             frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0,
+             kv_pool_pages: Optional[int] = None):
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -731,11 +889,28 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
     ``kv_dtype="fp8"`` keeps the KV cache as e4m3 codes with per-row fp32 scales (about half the
     bytes; head_dim 32, 64 or 128); ``None`` keeps it in the activation dtype.  A session is kept
-    per cache dtype."""
+    per cache dtype.
+
+    ``kv_page`` > 0 (a power of two in [16, 256]; head_dim 32, 64 or 128 on the GPU) keeps the
+    cache in pages of that many tokens (``PagedKVCache``): per layer and side one pool of
+    ``kv_pool_pages`` pages (default: ``B * ceil(t_max / kv_page)``, which cannot run out) and one
+    block table on the device, so a row occupies the pages its own length needs and not the
+    longest length any row might reach.  A paged call always runs the per-row path, as
+    ``prompt_lens`` does (without ``prompt_lens`` every row holds T0 ids), returns the tokens of
+    the unpaged per-row call, and composes with ``kv_dtype``, ``prefill_chunk`` and every sampling
+    form; pages are mapped on the host before each prefill piece, decode step or graph replay, and
+    a pool too small for the request raises ``RuntimeError`` there, before anything is launched.
+    0, the default, is the contiguous cache."""
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
     if prefill_chunk < 0:
         raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
+    if kv_page != 0:
+        _check_kv_page(kv_page)
+        if kv_pool_pages is not None and int(kv_pool_pages) < 1:
+            raise ValueError(f"generate: kv_pool_pages must be >= 1 (None: B * ceil(t_max / kv_page)), got {kv_pool_pages}")
+    elif kv_pool_pages is not None:
+        raise ValueError("generate: kv_pool_pages needs kv_page > 0")
     B, T0 = prompt.shape
     dev = prompt.device
     pen = _penalty_settings(B, repetition_penalty, presence_penalty, frequency_penalty)
@@ -753,9 +928,10 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
             raise ValueError("generate: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1, got "
                              f"{temperature}, {top_k}, {top_p}")
         sample = (float(temperature), int(top_k), float(top_p), int(seed)) if temperature > 0 else None
-    if prompt_lens is not None:
-        return _generate_ragged(model, prompt, _check_lens(prompt_lens, B, T0), max_new_tokens, eos_id, max_len,
-                                sample, prefill_chunk, kv_dtype, return_logprobs)
+    if prompt_lens is not None or kv_page:
+        lens = _check_lens(prompt_lens, B, T0) if prompt_lens is not None else [T0] * B
+        return _generate_ragged(model, prompt, lens, max_new_tokens, eos_id, max_len,
+                                sample, prefill_chunk, kv_dtype, return_logprobs, kv_page, kv_pool_pages)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype)
     out = [list(map(int, row)) for row in prompt.tolist()]
@@ -821,15 +997,19 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
 
 def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
-                     prefill_chunk: int = 0, kv_dtype: Optional[str] = None, return_logprobs: bool = False):
+                     prefill_chunk: int = 0, kv_dtype: Optional[str] = None, return_logprobs: bool = False,
+                     kv_page: int = 0, kv_pool_pages: Optional[int] = None):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
-    that has filled the cache frozen inside it (``_step_advance_rows``)."""
+    that has filled the cache frozen inside it (``_step_advance_rows``).  With ``kv_page`` the
+    cache is a ``PagedKVCache``: the pages of what a step (or a replay's steps) appends are
+    reserved on the host in front of it."""
     B = prompt.size(0)
     dev = prompt.device
     cap = min(model.args.maxlen, max_len or model.args.maxlen)     # total length at which a row stops
     t_max = min(cap, max(lens) + max_new_tokens)
-    cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype)
+    cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype, kv_page=kv_page,
+                             kv_pool_pages=kv_pool_pages)
     rows = prompt.tolist()
     out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
     lps = [[] for _ in range(B)]
@@ -877,6 +1057,8 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
             # for them (a finished row may run past its end: the kernels keep it in bounds)
             longest = max(n for n, d in zip(cache.lens, done) if not d)
             S = chunk if (max_new_tokens - n_gen >= chunk and longest + chunk <= t_max) else 1
+            if cache.page:   # the pages of the replay's S appends (the table is device data: no new capture)
+                cache.reserve(n + S for n in cache.lens)
             gkey = S if sample is None else (S, skey)
             g = graphs.get(gkey)
             if g is None:
@@ -894,6 +1076,8 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
                 if emit(row, lp):
                     return result()
         else:
+            if cache.page:
+                cache.reserve(n + 1 for n in cache.lens)
             nxt, _ = decode_step(model, nxt.view(B, 1), pos, cache, sample)
             cache.advance()
             if emit(nxt.tolist(), sample.logp.tolist() if pen else None):

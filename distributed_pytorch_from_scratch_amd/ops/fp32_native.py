@@ -105,6 +105,11 @@ _kv_append_chunk_q8 = reference._kv_append_chunk_q8
 _rope_append_q8 = reference._rope_append_q8
 _attn_decode_q8 = reference._attn_decode_q8
 _attn_extend_q8 = reference._attn_extend_q8
+# the paged KV cache ops likewise
+_kv_append_chunk_paged = reference._kv_append_chunk_paged
+_rope_append_paged = reference._rope_append_paged
+_attn_decode_paged = reference._attn_decode_paged
+_attn_extend_paged = reference._attn_extend_paged
 gemv_nt = reference.gemv_nt
 
 

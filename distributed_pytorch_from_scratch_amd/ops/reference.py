@@ -345,6 +345,95 @@ def _attn_extend_q8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: tor
     return _attn_extend(q, _kv_dequant(k8, ks), _kv_dequant(v8, vs), len, n, scale)
 
 
+# ----------------------------------------------------------------- paged KV cache ----
+# Storage (csrc/kernels/kv_page.h is the contract): per layer and side one pool (P, page, H, hd),
+# bf16 / fp32, or float8_e4m3fn with fp32 scale pools ks / vs (P, page, H); one block table tbl
+# int32 (B, MP), MP = ceil(t_max / page); key t of sequence b lives in pool row
+# tbl[b, t // page] * page + t % page, an entry that maps nothing is -1.  Always per-row: len [B].
+# An append through an entry outside [0, P) is dropped; a read through one takes page 0.
+
+def _paged_view(pool: torch.Tensor, tbl: torch.Tensor, t_max: int) -> torch.Tensor:
+    """The contiguous (B, t_max, ...) cache a pool (P, page, ...) holds through ``tbl`` (a copy)."""
+    P, page = pool.size(0), pool.size(1)
+    e = tbl.long()
+    e = torch.where((e >= 0) & (e < P), e, torch.zeros_like(e))
+    raw = pool.view(torch.uint8) if pool.dtype == torch.float8_e4m3fn else pool
+    g = raw[e]                                               # (B, MP, page, ...)
+    return g.reshape(e.size(0), e.size(1) * page, *pool.shape[2:])[:, :t_max].contiguous().view(pool.dtype)
+
+
+def _paged_put(pool: torch.Tensor, tbl: torch.Tensor, b: int, t0: int, rows: torch.Tensor) -> None:
+    """``rows`` (m, ...) become keys [t0, t0 + m) of sequence b: scattered through the table, rows
+    whose entry maps no page of the pool dropped."""
+    P, page = pool.size(0), pool.size(1)
+    t = torch.arange(t0, t0 + rows.size(0), device=pool.device)
+    e = tbl[b, t // page].long()
+    ok = (e >= 0) & (e < P)
+    dst = (e * page + t % page)[ok]
+    fp8 = pool.dtype == torch.float8_e4m3fn
+    flat = (pool.view(torch.uint8) if fp8 else pool).view(P * page, *pool.shape[2:])
+    src = rows.to(pool.dtype)
+    flat[dst] = (src.view(torch.uint8) if fp8 else src)[ok]
+
+
+def _kv_append_chunk_paged(qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                           ks: Optional[torch.Tensor], vs: Optional[torch.Tensor], tbl: torch.Tensor,
+                           len: torch.Tensor, n: Optional[torch.Tensor], t_max: int, page: int) -> None:
+    """``_kv_append_chunk`` (``ks`` / ``vs`` None) or ``_kv_append_chunk_q8`` into pools: what the
+    contiguous op writes at cache row len[b] + t goes to the pool row the table gives that key."""
+    P, PS, H, hd = k_pool.shape
+    assert PS == page and tbl.size(1) == -(-t_max // page), "pool / table do not fit (t_max, page)"
+    B = tbl.size(0)
+    assert len.numel() == B, "a paged cache is per-row: len must have B elements"
+    T = qkv.size(0) // B
+    rows = qkv.view(B, T, -1)
+    for b, (L, m) in enumerate(_chunk_rows(len, n, B, T, t_max)):
+        if m == 0:
+            continue
+        kx = rows[b, :m, H * hd: 2 * H * hd].view(m, H, hd)
+        vx = rows[b, :m, 2 * H * hd: 3 * H * hd].view(m, H, hd)
+        if ks is None:
+            _paged_put(k_pool, tbl, b, L, kx)
+            _paged_put(v_pool, tbl, b, L, vx)
+        else:
+            for x, pool, sc in ((kx, k_pool, ks), (vx, v_pool, vs)):
+                codes, inv = _kv_quant_rows(x)
+                _paged_put(pool, tbl, b, L, codes)
+                _paged_put(sc, tbl, b, L, inv)
+
+
+def _rope_append_paged(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
+                       v_pool: torch.Tensor, ks: Optional[torch.Tensor], vs: Optional[torch.Tensor],
+                       tbl: torch.Tensor, len: torch.Tensor, t_max: int, page: int) -> None:
+    """rope_ on the q and k heads of the packed rows [B, 3*H*hd], then the (quantising) append of
+    the rotated k row and the v row at key len[b] of the pools (a full row appends nothing)."""
+    H, hd = k_pool.size(2), k_pool.size(3)
+    rope_(qkv, pos, table, 2 * H, hd, False)
+    _kv_append_chunk_paged(qkv, k_pool, v_pool, ks, vs, tbl, len, None, t_max, page)
+
+
+def _attn_decode_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, ks: Optional[torch.Tensor],
+                       vs: Optional[torch.Tensor], tbl: torch.Tensor, len: torch.Tensor, t_max: int, page: int,
+                       scale: float) -> torch.Tensor:
+    """``attn_decode`` (per-row) / ``_attn_decode_q8`` on the contiguous view of the pools."""
+    assert k_pool.size(1) == page and len.numel() == tbl.size(0)
+    kc, vc = _paged_view(k_pool, tbl, t_max), _paged_view(v_pool, tbl, t_max)
+    if ks is None:
+        return attn_decode(q, kc, vc, len, scale)
+    return _attn_decode_q8(q, kc, vc, _paged_view(ks, tbl, t_max), _paged_view(vs, tbl, t_max), len, scale)
+
+
+def _attn_extend_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, ks: Optional[torch.Tensor],
+                       vs: Optional[torch.Tensor], tbl: torch.Tensor, len: torch.Tensor, n: Optional[torch.Tensor],
+                       t_max: int, page: int, scale: float) -> torch.Tensor:
+    """``_attn_extend`` / ``_attn_extend_q8`` on the contiguous view of the pools."""
+    assert k_pool.size(1) == page and len.numel() == tbl.size(0)
+    kc, vc = _paged_view(k_pool, tbl, t_max), _paged_view(v_pool, tbl, t_max)
+    if ks is None:
+        return _attn_extend(q, kc, vc, len, n, scale)
+    return _attn_extend_q8(q, kc, vc, _paged_view(ks, tbl, t_max), _paged_view(vs, tbl, t_max), len, n, scale)
+
+
 def gemv_nt_ok(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> bool:
     return True
 

@@ -8,6 +8,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
                                  [--prefill-chunk N [N ...]] [--continuation --t0 1024 --chunk 256]
                                  [--kv-dtype {act,fp8,both}] [--modes graph eager]
                                  [--penalties R,P,F] [--logprobs]
+                                 [--ragged --kv-page N [N ...]]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -46,6 +47,10 @@ of the sampling launch (``generate(..., repetition_penalty=R, ..., return_logpro
 same interleaved rounds: every round then times the call as the other flags give it and the same
 call with the penalties / log-probabilities, and the lines of the latter carry ``"form": "pen"``.
 ``--sample-kernel --penalties R,P,F`` times the ``_sample_logits_pen`` launch alone.
+
+``--ragged --kv-page N [N ...]`` decodes the ragged batch with the paged KV cache
+(``generate(..., kv_page=N)``) at every N next to the contiguous per-row cache, in the same
+process and interleaved rounds, and then times the decode-attention launch alone (``paged_bench``).
 """
 from __future__ import annotations
 
@@ -86,7 +91,11 @@ def main():
     ap.add_argument("--penalties", default=None, metavar="R,P,F",
                     help="repetition,presence,frequency: also time the penalised form in the same rounds")
     ap.add_argument("--logprobs", action="store_true", help="the penalised form returns log-probabilities")
+    ap.add_argument("--kv-page", type=int, nargs="+", default=None, metavar="N",
+                    help="--ragged: the paged KV cache at these page sizes next to the contiguous one")
     a = ap.parse_args()
+    if a.kv_page and not a.ragged:
+        ap.error("--kv-page runs the ragged decode benchmark: give --ragged")
     pen_kw = {}
     if a.penalties:
         r, p_, f = (float(v) for v in a.penalties.split(","))
@@ -126,6 +135,8 @@ def main():
         return continuation_bench(a, m)
     if a.prefill_chunk:
         return prefill_bench(a, m)
+    if a.kv_page:
+        return paged_bench(a, m)
     for B in a.batch:
         prompt = torch.randint(0, args.vocab_size, (B, a.prompt), device="cuda")
         lens = None
@@ -227,6 +238,92 @@ def _timed(fn):
 def _median(v):
     v = sorted(v)
     return v[len(v) // 2]
+
+
+def paged_bench(a, m):
+    """``--ragged --kv-page N [N ...]``: the ragged batch of ``main`` decoded with the contiguous
+    per-row cache (page 0) and with the paged cache at every N, in one process and interleaved
+    rounds (``--repeats`` of them, every session warm; ``--kv-dtype`` chooses the storage).  The
+    paged sessions get the pages the batch needs (``kv_pool_pages`` = the sum over the rows of
+    ceil((len + new) / N)), so ``cache_bytes`` shows what paging saves against the slab.  One line
+    per (batch, mode, page) with the rounds, their median and spread; then the decode-attention
+    launch alone (``attn_decode`` per-row against ``_attn_decode_paged``) at T_max 1024, 200
+    launches per graph replay."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.models import generation as G
+    from distributed_pytorch_from_scratch_amd.ops import _ext
+    kd = None if a.kv_dtype == "act" else "fp8"
+    pages = [0] + list(a.kv_page)
+    for B in a.batch:
+        prompt = torch.randint(0, m.args.vocab_size, (B, a.prompt), device="cuda")
+        lo = max(1, a.prompt // 4)
+        lens = [lo + b * (a.prompt - lo) // max(1, B - 1) for b in range(B)] if B > 1 else [a.prompt]
+        need = {p: sum(-(-(n + a.new) // p) for n in lens) for p in pages if p}
+        kws = {p: dict(kv_page=p, kv_pool_pages=need[p]) if p else {} for p in pages}
+        for mode in a.modes:
+            os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
+            run = lambda p: G.generate(m, prompt, max_new_tokens=a.new, prompt_lens=lens, kv_dtype=kd, **kws[p])
+            toks = {p: run(p) for p in pages}                       # warm-up: GEMM choices, graph capture
+            ms = {p: [] for p in pages}
+            for _ in range(a.repeats):
+                for p in pages:                                     # interleaved rounds
+                    ms[p].append(round(_timed(lambda: run(p)) / a.new, 4))
+            kept = {(k[6] if len(k) > 6 else 0): e["cache"].nbytes() for k, e in G._SESSIONS.items()}
+            for p in pages:
+                print(json.dumps({"bench": "kv_page", "model": a.model, "batch": B, "mode": mode, "prompt": a.prompt,
+                                  "new": a.new, "min_len": min(lens), "max_len": max(lens), "kv_dtype": kd or "act",
+                                  "kv_page": p, "kv_pool_pages": need.get(p), "ms_per_step": ms[p],
+                                  "ms_per_step_median": _median(ms[p]), "ms_per_step_spread": round(max(ms[p]) - min(ms[p]), 4),
+                                  "tokens_per_s_median": round(B / _median(ms[p]) * 1000, 1),
+                                  "cache_bytes": kept.get(p), "same_tokens_as_contiguous": toks[p] == toks[0]}),
+                      flush=True)
+        G.clear_sessions()
+    # the decode-attention launch alone
+    C = _ext.require()
+    attn = m.layers[0].attn
+    H, hd, t_max = attn.num_local_heads, attn.head_dim, 1024
+    for B in a.batch:
+        kc, vc = (torch.randn(B, t_max, H, hd, device="cuda").bfloat16() for _ in range(2))
+        q = torch.randn(B, 3 * H * hd, device="cuda").bfloat16()
+        lens = torch.tensor([t_max // 4 + b * (3 * t_max // 4 - 1) // max(1, B - 1) for b in range(B)], dtype=torch.int32,
+                            device="cuda")
+        launch = {0: lambda: C.attn_decode(q, kc, vc, lens, hd ** -0.5)}
+        for p in a.kv_page:
+            MP = t_max // p
+            tbl = torch.randperm(B * MP, device="cuda").int().view(B, MP)
+            kp, vp = (torch.empty(B * MP, p, H, hd, dtype=torch.bfloat16, device="cuda") for _ in range(2))
+            for pool, c in ((kp, kc), (vp, vc)):
+                pool[tbl.long().flatten()] = c.view(B * MP, p, H, hd)
+            launch[p] = (lambda kp=kp, vp=vp, tbl=tbl, p=p:
+                         C._attn_decode_paged(q, kp, vp, None, None, tbl, lens, t_max, p, hd ** -0.5))
+            assert torch.equal(launch[p](), launch[0]())
+        graphs = {}
+        for p, fn in launch.items():
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(3):
+                    fn()
+            torch.cuda.current_stream().wait_stream(s)
+            graphs[p] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[p]):
+                for _ in range(200):
+                    fn()
+            graphs[p].replay()
+        us = {p: [] for p in launch}
+        for _ in range(max(a.repeats, 5)):
+            for p, g in graphs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                us[p].append(round(5 * e0.elapsed_time(e1), 2))
+        for p in launch:
+            print(json.dumps({"bench": "kv_page_attn", "kernel": "_attn_decode_paged" if p else "attn_decode", "batch": B,
+                              "heads": H, "head_dim": hd, "t_max": t_max, "kv_page": p, "us_per_call": us[p],
+                              "us_per_call_median": _median(us[p]),
+                              "us_per_call_spread": round(max(us[p]) - min(us[p]), 2)}), flush=True)
 
 
 def prefill_bench(a, m):
