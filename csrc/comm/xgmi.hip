@@ -19,7 +19,9 @@
 // allocation [in | tmp] and one uncached signal allocation; handles are exchanged over the
 // c10d store by the Python side (parallel/xgmi.py).  Workgroup b of every rank owns the same
 // vector range in every phase, so the barriers are per workgroup: b signals its peers' b and
-// waits for their b (no grid-wide barrier, no residency assumption).  Flags are monotonic
+// waits for their b (no grid-wide barrier; within a rank no workgroup waits for another, but
+// workgroup b of EVERY rank must be resident at once: given with one rank per GPU, and where
+// ranks share a GPU parallel/xgmi.py caps the grid so that all of them fit).  Flags are monotonic
 // epochs (one per call, identical on every rank because every rank issues the same call
 // sequence), compared wrap-safe, never reset.
 //

@@ -287,10 +287,12 @@ def _decide(t: torch.Tensor, p) -> Optional[_Choice]:
     # size per class.  xGMI workgroups per call (1024 threads each): every CU that holds one
     # cannot also hold a 2-wave-per-SIMD GEMM block, so per (op, class) take the narrowest grid
     # within 10 % of the fastest one measured in isolation.
-    G = len(_GRIDS)
     xg = "xgmi" in comms
-    cols = ["rccl"] + [k for k in kl if k != "xgmi"] + ([f"xgmi/{nb}" for nb in _GRIDS] if xg else []) \
-        + ([f"xgmi1/{nb}" for nb in _GRIDS] if one_shot else [])
+    # (ranks sharing a GPU: only the widths that fit it together, XgmiComm.max_blocks)
+    xmax = comms["xgmi"].max_blocks if xg else None
+    grids = tuple(nb for nb in _GRIDS if xmax is None or nb <= xmax) or (xmax,)
+    cols = ["rccl"] + [k for k in kl if k != "xgmi"] + ([f"xgmi/{nb}" for nb in grids] if xg else []) \
+        + ([f"xgmi1/{nb}" for nb in grids] if one_shot else [])
     NC = len(SIZE_CLASSES)
     times = torch.full((3, NC, len(cols)), float("inf"), device=t.device)
     timed = m == "auto" and (backend == "nccl" or any_be)
@@ -366,8 +368,9 @@ def _decide(t: torch.Tensor, p) -> Optional[_Choice]:
                 xt = [row[j] for j in js]
                 if min(xt) == float("inf"):
                     continue
-                jx = min(j for j, tt in enumerate(xt) if tt <= 1.1 * min(xt)) if timed else _GRIDS.index(32)
-                grid[kind] = _GRIDS[jx]
+                jx = min(j for j, tt in enumerate(xt) if tt <= 1.1 * min(xt)) if timed \
+                    else max(j for j, nb in enumerate(grids) if nb <= 32 or j == 0)
+                grid[kind] = grids[jx]
                 cand[kind] = xt[jx]
             if m == "auto":
                 fastest = min(cand, key=cand.get)

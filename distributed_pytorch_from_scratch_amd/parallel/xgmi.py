@@ -19,6 +19,8 @@ in-node transport, with identical semantics (sum / concatenate over the TP group
 from __future__ import annotations
 
 import os
+import socket
+from collections import Counter
 from typing import List, Optional
 
 import torch
@@ -69,10 +71,23 @@ class XgmiComm:
             self.h, handle = C.xgmi_create(self.rank, self.world, cap, self.nslots)
         except Exception as e:   # noqa: BLE001
             handle, err = b"", f"{type(e).__name__}: {e}"
-        handles: List[Optional[bytes]] = [None] * self.world
-        dist.all_gather_object(handles, handle, group=group)
+        pr = torch.cuda.get_device_properties(torch.cuda.current_device())
+        where = (socket.gethostname(), pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id)
+        gathered: List[Optional[tuple]] = [None] * self.world
+        dist.all_gather_object(gathered, (handle, where, pr.multi_processor_count), group=group)
+        handles = [g[0] for g in gathered]
         if not all(handles):
             self._abort(f"xGMI buffers could not be allocated on every rank ({err or 'a peer failed'})")
+        # Workgroup b of a call waits for workgroup b of every peer, so all of them must be on
+        # the device at once.  One rank per GPU has its GPU to itself; ranks that share a GPU
+        # (the one-GPU rehearsal) share its CUs, and a 1024-thread workgroup of these kernels
+        # takes a CU to itself (register use), so the grid is capped at the CUs over the ranks
+        # on the device: past it the first ranks to launch fill the device and spin on peers
+        # that can never be dispatched.  Computed from gathered values: equal on every rank.
+        # The other TP groups of the WORLD are taken to be laid out like this one.
+        sharing = max(Counter(g[1] for g in gathered).values())
+        self.sharing = sharing if sharing == 1 else sharing * (dist.get_world_size() // self.world)
+        self.max_blocks = None if sharing == 1 else max(1, min(g[2] for g in gathered) // self.sharing)
         try:
             C.xgmi_open(self.h, b"".join(handles))
         except Exception as e:   # noqa: BLE001
@@ -81,14 +96,13 @@ class XgmiComm:
         dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)
         if ok.item() == 0:
             self._abort(f"xGMI peer buffers could not be mapped on every rank ({err or 'a peer failed'})")
-        blocks = blocks or int(os.environ.get("DPFS_XGMI_BLOCKS", "32"))
-        C.xgmi_set_blocks(self.h, blocks)
-        self._blocks = blocks
+        self.set_blocks(blocks or int(os.environ.get("DPFS_XGMI_BLOCKS", "32")))
         # per-op grid width (tp_comm picks one per op); None = the communicator default
         self.op_blocks = {"all_reduce": None, "reduce_scatter": None, "all_gather": None}
         # High-priority side stream: a collective that overlaps compute is the critical path
-        # of the other chunk, so its (narrow) kernel should win the CU arbitration.
-        self.stream = torch.cuda.Stream(priority=-1)
+        # of the other chunk, so its (narrow) kernel should win the CU arbitration.  (Ranks
+        # sharing a GPU wait for each other's collectives: none of them may outrank another.)
+        self.stream = torch.cuda.Stream(priority=-1 if self.sharing == 1 else 0)
         dev = torch.device("cuda", torch.cuda.current_device())
         # Staging slots: producer GEMMs write their output straight into one (``staging``), so
         # the reduce-scatter / all-reduce of it skips the copy-in.
@@ -205,9 +219,11 @@ class XgmiComm:
         return work
 
     def set_blocks(self, blocks: int):
-        """Workgroups per collective launch (must be equal on every rank of the group)."""
-        self.C.xgmi_set_blocks(self.h, int(blocks))
-        self._blocks = int(blocks)
+        """Workgroups per collective launch (must be equal on every rank of the group); at most
+        ``max_blocks`` where ranks share a GPU."""
+        blocks = int(blocks) if self.max_blocks is None else min(int(blocks), self.max_blocks)
+        self.C.xgmi_set_blocks(self.h, blocks)
+        self._blocks = blocks
 
     # --------------------------------------------------------------------- health ----
     def error(self) -> int:
