@@ -140,6 +140,54 @@ torch::Tensor gemv_nt(torch::Tensor x, torch::Tensor w, c10::optional<torch::Ten
   return y;
 }
 
+// ------------------------------------------------------------------- fp8 weights (decode) --
+// Weight-only e4m3 projections (kernels/gemv_w8.hip): codes uint8 [N, K] with one fp32 scale inv
+// [N] per output channel, value = f32(code) * inv[n].  Bound with leading underscores and recorded
+// in tests/golden/ext_api_w8.txt (tests/test_ext_api_w8.py).
+bool gemv_nt_w8_ok(torch::Tensor x, torch::Tensor codes, bool swiglu) {
+  if (!x.is_cuda() || !codes.is_cuda() || x.dim() != 2 || codes.dim() != 2 || x.scalar_type() != torch::kBFloat16 ||
+      codes.scalar_type() != torch::kUInt8 || x.stride(1) != 1 || codes.stride(1) != 1 || x.device() != codes.device())
+    return false;
+  const int64_t K = codes.size(1);
+  if (x.size(1) != (swiglu ? 2 * K : K) || codes.size(0) >= (1LL << 31) || K >= (1LL << 31)) return false;
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 || reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16)
+    return false;   // 16-byte operand loads
+  return dpfs_gemv_w8_ok((int)x.size(0), (int)codes.size(0), (int)K, x.stride(0), codes.stride(0)) != 0;
+}
+
+// y[M, N] = bf16((a codes^T) * inv + bias) for M <= 64, a = x or with swiglu silu(gate) * up of the
+// packed x = [gate | up]; fp32 accumulation, the scale applied once per output column.
+torch::Tensor gemv_nt_w8(torch::Tensor x, torch::Tensor codes, torch::Tensor inv, c10::optional<torch::Tensor> bias,
+                         bool swiglu) {
+  TORCH_CHECK(gemv_nt_w8_ok(x, codes, swiglu),
+              "gemv_nt_w8: needs bf16 row-major x [M <= 64, K or 2K] (row stride % 8 == 0) and uint8 codes [N, K] "
+              "(row stride % 16 == 0) on one device, both 16-byte aligned, K % 64 == 0");
+  const int64_t M = x.size(0), N = codes.size(0), K = codes.size(1);
+  const at::DeviceGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  dpfs_gemv_w8(x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), opt_f32(inv, N, "inv"),
+               opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M, (int)N, (int)K, swiglu ? 1 : 0, stream());
+  return y;
+}
+
+// (codes uint8 [N, K], inv fp32 [N]) of a bf16 weight [N, K], one row per output channel, in the
+// row format of kernels/kv8.h: the bytes of ops/reference.py:_quant_w8_rows.
+std::vector<torch::Tensor> quant_w8_rows(torch::Tensor w) {
+  check_cuda(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == torch::kBFloat16 && w.stride(1) == 1 && w.size(1) % 8 == 0 &&
+                  w.size(1) > 0 && (w.size(0) <= 1 || (w.stride(0) % 8 == 0 && w.stride(0) >= w.size(1))) &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && w.size(0) < (1LL << 31) &&
+                  w.size(1) < (1LL << 31),
+              "quant_w8_rows: w must be a 16-byte aligned bf16 [N, K] with unit column stride, K % 8 == 0 and a row "
+              "stride % 8 == 0");
+  const int64_t N = w.size(0), K = w.size(1);
+  const at::DeviceGuard g(w.device());
+  auto codes = torch::empty({N, K}, w.options().dtype(torch::kUInt8));
+  auto inv = torch::empty({N}, w.options().dtype(torch::kFloat32));
+  dpfs_quant_w8_rows(w.data_ptr(), w.stride(0), codes.data_ptr(), K, inv.data_ptr<float>(), (int)N, (int)K, stream());
+  return {codes, inv};
+}
+
 // rope_ on the q and k heads of the packed qkv rows + kv_append of the rotated k and v rows
 // at *len, one kernel (decode step).
 void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kc, torch::Tensor vc,
@@ -668,6 +716,10 @@ void bind_decode(py::module_& m) {
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("_gemv_nt_w8_ok", &gemv_nt_w8_ok, py::arg("x"), py::arg("codes"), py::arg("swiglu") = false);
+  m.def("_gemv_nt_w8", &gemv_nt_w8, py::arg("x"), py::arg("codes"), py::arg("inv"), py::arg("bias") = py::none(),
+        py::arg("swiglu") = false);
+  m.def("_quant_w8_rows", &quant_w8_rows, py::arg("w"));
   m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("len"));
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),

@@ -244,6 +244,14 @@ int dpfs_gemm_tn_group(int n, const void* const* A, const void* const* B, float*
                        const void* const* A2, const void* const* B2, const int* lda2, const int* ldb2, int K1,
                        hipStream_t s);
 
+// kernels/gemv_w8.hip
+// weight-only fp8 decode projections: e4m3 codes [N, K] (row stride ldc bytes) with fp32 inv [N]
+int dpfs_gemv_w8_ok(int M, int N, int K, long long lda, long long ldc);
+void dpfs_gemv_w8(const void* A, long long lda, const void* codes, long long ldc, const float* inv,
+                  const float* bias, void* Y, long long ldy, int M, int N, int K, int swiglu, hipStream_t s);
+void dpfs_quant_w8_rows(const void* W, long long ldw, void* codes, long long ldc, float* inv, int N, int K,
+                        hipStream_t s);
+
 // kernels/kv8.hip
 void dpfs_kv_append_chunk_q8(const void* ksrc, const void* vsrc, long long ld, void* k8, void* v8, float* ks,
                              float* vs, const int* len, int len_rows, const int* n, int B, int T, int H, int HD,

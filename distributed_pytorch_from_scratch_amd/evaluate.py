@@ -93,6 +93,9 @@ def get_test_args(argv=None):
                    help="prefill a prompt in pieces of at most this many tokens (0: whole)")
     g.add_argument("--kv_cache_dtype", choices=["act", "fp8"], default="act",
                    help="KV cache storage: the activation dtype, or e4m3 codes with per-row fp32 scales")
+    g.add_argument("--weight_dtype", choices=["act", "fp8"], default="act",
+                   help="projection weights of the one-token decode steps: the activation dtype, or e4m3 codes "
+                        "with one fp32 scale per output channel (KV-cached decoding; the prefill keeps bf16)")
     g.add_argument("--kv_page", type=int, default=0,
                    help="keep the KV cache in pages of this many tokens (a power of two in [16, 256]; 0: contiguous)")
     g.add_argument("--kv_pool_pages", type=int, default=0,
@@ -122,7 +125,8 @@ def calc_loss(model: Transformer, dataloader, dev) -> float:
 def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: int, dev, kv_cache: bool = True,
                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                   prefill_chunk: int = 0, kv_dtype=None, repetition_penalty=1.0, presence_penalty=0.0,
-                  frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None):
+                  frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None,
+                  weight_dtype=None):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
@@ -147,7 +151,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
                        top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype,
                        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                        frequency_penalty=frequency_penalty, return_logprobs=return_logprobs, kv_page=kv_page,
-                       kv_pool_pages=kv_pool_pages)
+                       kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype)
         out, lps = (out[0][0], out[1][0]) if return_logprobs else (out[0], None)
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
@@ -170,7 +174,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
 def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
                         top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None,
                         repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None):
+                        return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None, weight_dtype=None):
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
@@ -188,7 +192,8 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
         row = lambda v, b: [v[b]] if seq(v) else v                # a prompt's own value, still per row
         return [greedy_decode(model, p, bos, eos, max_len, dev, True, row(temperature, b), row(top_k, b),
                               row(top_p, b), row(seed, b), prefill_chunk, kv_dtype, repetition_penalty,
-                              presence_penalty, frequency_penalty, return_logprobs, kv_page, kv_pool_pages)
+                              presence_penalty, frequency_penalty, return_logprobs, kv_page, kv_pool_pages,
+                              weight_dtype)
                 for b, p in enumerate(prompts)]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
@@ -197,7 +202,8 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, prompt_lens=lens,
                     prefill_chunk=prefill_chunk, kv_dtype=kv_dtype, repetition_penalty=repetition_penalty,
                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                    return_logprobs=return_logprobs, kv_page=kv_page, kv_pool_pages=kv_pool_pages)
+                    return_logprobs=return_logprobs, kv_page=kv_page, kv_pool_pages=kv_pool_pages,
+                    weight_dtype=weight_dtype)
     outs, lps = outs if return_logprobs else (outs, [None] * len(prompts))
     res = []
     for p, out, lp in zip(prompts, outs, lps):
@@ -266,6 +272,8 @@ def test(rank, args):
                     prefill_chunk=args.prefill_chunk)
     if args.kv_cache_dtype != "act":
         sampling["kv_dtype"] = args.kv_cache_dtype
+    if args.weight_dtype != "act":
+        sampling["weight_dtype"] = args.weight_dtype
     pens = dict(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                 frequency_penalty=args.frequency_penalty)
     if pens != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
@@ -335,6 +343,8 @@ def main(argv=None):
         raise ValueError("--prefill_chunk must be >= 0, and > 0 chunks the KV-cached prefill: drop --no_kv_cache")
     if args.kv_cache_dtype != "act" and args.no_kv_cache:
         raise ValueError("--kv_cache_dtype chooses the storage of the KV cache: drop --no_kv_cache")
+    if args.weight_dtype != "act" and args.no_kv_cache:
+        raise ValueError("--weight_dtype chooses the weights of the KV-cached decode steps: drop --no_kv_cache")
     check_kv_page_args(args)
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)

@@ -56,6 +56,13 @@ pages from a free list in front of every prefill piece, decode step or graph rep
 table from device memory and are safe for any table content, so the mapping is device data like
 the lengths and a session's graphs are captured once.
 
+fp8 weights (``weight_dtype="fp8"``; the default ``None`` keeps the bf16 weights): the projections of
+the one-token steps (QKV, Wo, gate|up, down with the fused SwiGLU, lm_head) read weight-only e4m3
+codes with one fp32 scale per output channel (``quantise_weights``; ``_gemv_nt_w8``,
+csrc/kernels/gemv_w8.hip), quantised once per session and kept on its cache (``cache.w8``).  The
+prefill and the extend pieces keep the bf16 weights: they are compute-bound, only the one-token
+steps are bound by the weight bytes.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -88,6 +95,7 @@ class KVCache:
     row scales ``ks`` / ``vs`` ``(B, T_max, H_local)`` (head_dim 32, 64 or 128)."""
 
     page = 0    # the page size of a ``PagedKVCache``; 0: this contiguous form
+    w8 = None   # fp8 decode weights of the session (``quantise_weights``); None: bf16 weights
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
                  ragged: bool = False, kv_dtype: Optional[str] = None):
@@ -336,6 +344,41 @@ class SamplePen(SampleRows):
         self.hist.zero_()
         self.hist.scatter_(1, idx, -2 ** 31)
         return self
+
+
+W8_MAX_BATCH = 64     # rows of the fp8-weight projection kernel (gemv_w8_k: four 16-row MFMA tiles)
+
+
+def _check_weight_dtype(model, B: int, weight_dtype, who: str = "generate") -> None:
+    if weight_dtype not in (None, "fp8"):
+        raise ValueError(f"{who}: weight_dtype must be None (the activation dtype) or 'fp8', got {weight_dtype!r}")
+    if weight_dtype is None:
+        return
+    if B > W8_MAX_BATCH:
+        raise ValueError(f"{who}: weight_dtype='fp8' decodes at most {W8_MAX_BATCH} sequences per batch, got {B}")
+    if model.args.norm != "rmsnorm":
+        raise ValueError(f"{who}: weight_dtype='fp8' needs the RMSNorm model (norm={model.args.norm!r} decodes "
+                         "through the module layers, which keep their own weights)")
+    if model.compute_dtype == torch.float32:
+        raise ValueError(f"{who}: weight_dtype='fp8' needs bf16 compute (the codes feed bf16 MFMAs), the model is "
+                         "set to fp32 compute")
+
+
+def quantise_weights(model, dev) -> dict:
+    """The projection weights of the decode step (QKV, Wo, gate|up, down of every layer and the
+    lm_head; under TP this rank's shards) as weight-only fp8: ``{id(parameter): (codes uint8
+    [N, K], inv fp32 [N])}``, one scale per output row (``ops/reference.py:_quant_w8_rows``),
+    quantised from the compute copy of the parameter by ``_quant_w8_rows``.  A weight whose K is
+    not a multiple of 64 is left out: its projection keeps the bf16 route."""
+    from .engine_common import _Layer
+    dev = torch.device(dev)
+    dt = model.act_dtype(dev)
+    k = K(model.embedding.weight, dt)
+    ws = [model.lm_head.weight]
+    for layer in model.layers:
+        L = _Layer(layer)
+        ws += [L.wqkv, L.wo, L.wgu, L.wd]
+    return {id(w): tuple(k._quant_w8_rows(shadow(w, dt))) for w in ws if w.size(1) % 64 == 0}
 
 
 def _penalty_settings(B: int, repetition_penalty, presence_penalty, frequency_penalty):
@@ -593,6 +636,8 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     host state: graph-capturable."""
     from .engine_common import _Layer
     if model.args.norm != "rmsnorm":
+        if cache.w8 is not None:
+            raise ValueError("decode_step: fp8 weights need the RMSNorm model")
         return _decode_step_modules(model, ids, pos, cache, sample)
     B = ids.size(0)
     dev = ids.device
@@ -604,8 +649,19 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     tab = model.rope_table(dev)
     pend = pend_bias = None
     small = B <= 16
+    w8 = cache.w8 or {}
 
     def proj(a, w, bias=None, swiglu=False):
+        # fp8 weights (cache.w8, B <= 64): gemv_w8_k on the session's codes of this parameter.  A
+        # projection without codes (K % 64 != 0) or whose operands the kernel declines (a pinned
+        # library backend) keeps the bf16 route below; with d, the local head width and the local
+        # ffn width all multiples of 64 no projection falls back.
+        q = w8.get(id(w))
+        if q is not None:
+            y = GS.small_nt_w8(k, a, q, bias, swiglu)
+            if y is not None:
+                return y
+        w = W(w)
         if small:   # MFMA GEMV-class kernel, SwiGLU fused into the down projection's operand
             return GS.small_nt(k, a, w, bias, swiglu)
         return GS.gemm_nt(k, k.swiglu_fwd(a) if swiglu else a, w, bias)
@@ -619,7 +675,7 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
             h1, _ = k.rmsnorm_fwd(x, L.s1, L.eps1)
         else:
             x, h1, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, L.s1, L.eps1)
-        qkv = proj(h1, W(L.wqkv), L.bqkv)
+        qkv = proj(h1, L.wqkv, L.bqkv)
         if cache.page:  # through the block table; head_dim 32 / 64 / 128: always the fused kernel
             pools = (cache.k[li], cache.v[li], *cache.scales(li), cache.tbl, cache.len_t, cache.t_max, cache.page)
             k._rope_append_paged(qkv, pos, tab, *pools)
@@ -635,13 +691,13 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
                 k.rope_(qkv, pos, tab, 2 * L.h, L.hd, False)
                 k.kv_append(qkv, cache.k[li], cache.v[li], cache.len_t)
             o = k.attn_decode(qkv, cache.k[li], cache.v[li], cache.len_t, 1.0 / math.sqrt(L.hd))
-        pout = proj(o, W(L.wo))
+        pout = proj(o, L.wo)
         tp_comm.all_reduce(pout, async_op=False)
         x, h2, _ = k.add_rmsnorm_fwd(pout, L.bo, x, L.s2, L.eps2)
-        pend, pend_bias = proj(proj(h2, W(L.wgu), L.bgu), W(L.wd), swiglu=True), L.bd
+        pend, pend_bias = proj(proj(h2, L.wgu, L.bgu), L.wd, swiglu=True), L.bd
         tp_comm.all_reduce(pend, async_op=False)
     _, hfin, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, model.norm.scale, model.norm.eps)
-    logits = proj(hfin, W(model.lm_head.weight), model.lm_head.bias)
+    logits = proj(hfin, model.lm_head.weight, model.lm_head.bias)
     nxt, logits = _pick(model, comm_ops.Gather.apply(logits, model.lm_head.sizes), pos, sample)
     _advance(cache, pos)
     return nxt, logits
@@ -774,7 +830,7 @@ _SESSIONS = {}   # (id(model), B, t_max, device, kv_dtype, ragged[, kv_page, kv_
 
 
 def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Optional[str] = None,
-             kv_page: int = 0, kv_pool_pages: Optional[int] = None):
+             kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
     """The KV cache and decode graphs for this (model, batch, length, cache dtype, uniform /
     ragged, page size, pool pages): reused
     by the next generate() call of the same shape, so serving pays the graph capture once (a
@@ -785,11 +841,17 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     DPFS_DECODE_SESSION_MAX_GB (default 16; an fp8 cache counts codes and scales, a paged one its
     pools and table) are kept; ``clear_sessions()`` frees them.  A paged cache (``kv_page`` > 0) is
     a form of the cache like its dtype: its key is the unpaged key followed by (kv_page,
-    kv_pool_pages), and the paged sessions of the kept shape stay beside the unpaged ones."""
+    kv_pool_pages), and the paged sessions of the kept shape stay beside the unpaged ones.  fp8 weights
+    (``weight_dtype="fp8"``) are a form of the session too: the key ends in ("weights", "fp8"),
+    behind everything the shape comparison below indexes; the codes (``quantise_weights``) hang on
+    the session's cache as ``cache.w8``, its graphs replay them, and like the graphs they are
+    rebuilt with the session when any parameter's version moves."""
     attn0 = model.layers[0].attn
     key = (id(model), B, t_max, str(dev), kv_dtype, ragged)
     if kv_page:
         key += (kv_page, kv_pool_pages)
+    if weight_dtype:
+        key += (("weights", weight_dtype),)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
@@ -801,6 +863,8 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     else:
         cache = KVCache(len(model.layers), B, t_max, attn0.num_local_heads, attn0.head_dim, model.act_dtype(dev), dev,
                         ragged, kv_dtype)
+    if weight_dtype == "fp8":
+        cache.w8 = quantise_weights(model, dev)
     graphs = {}
     kv_bytes = cache.nbytes()             # the fp8 form: codes and scales; the paged form: pools and table
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
@@ -837,7 +901,7 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
              seed=0, prompt_lens=None, prefill_chunk: int = 0,
              kv_dtype: Optional[str] = None, repetition_penalty=1.0, presence_penalty=0.0,
              frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0,
-             kv_pool_pages: Optional[int] = None):
+             kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -900,7 +964,21 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     the unpaged per-row call, and composes with ``kv_dtype``, ``prefill_chunk`` and every sampling
     form; pages are mapped on the host before each prefill piece, decode step or graph replay, and
     a pool too small for the request raises ``RuntimeError`` there, before anything is launched.
-    0, the default, is the contiguous cache."""
+    0, the default, is the contiguous cache.
+
+    ``weight_dtype="fp8"`` runs the projections of every one-token decode step (QKV, Wo, gate|up,
+    down with the fused SwiGLU, lm_head) on weight-only e4m3 codes with one fp32 scale per output
+    channel (``_quant_w8_rows``; ``_gemv_nt_w8``, csrc/kernels/gemv_w8.hip: half the weight bytes
+    per token).  Every parameter is quantised once per session (``quantise_weights``) and again
+    when a weight changes.  Batches of up to 64 sequences; a projection whose K is not a multiple
+    of 64 keeps its bf16 weights (none does when d, the local head width and the local ffn width
+    are multiples of 64).  The prefill, whole or chunked, keeps the bf16 weights: it is
+    compute-bound, only the one-token steps are weight-bound.  Composes with ``kv_dtype``,
+    ``kv_page``, ``prompt_lens``, ``prefill_chunk``, every sampling form and TP > 1 (each rank
+    quantises its own shard; a row-parallel partial sum is scaled before the all-reduce).
+    ``ValueError`` for a batch above 64, the LayerNorm model and fp32 compute.  On the CPU the
+    oracle ops run.  ``None``, the default, is every path above unchanged."""
+    _check_weight_dtype(model, prompt.size(0), weight_dtype)
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
     if prefill_chunk < 0:
@@ -931,9 +1009,10 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     if prompt_lens is not None or kv_page:
         lens = _check_lens(prompt_lens, B, T0) if prompt_lens is not None else [T0] * B
         return _generate_ragged(model, prompt, lens, max_new_tokens, eos_id, max_len,
-                                sample, prefill_chunk, kv_dtype, return_logprobs, kv_page, kv_pool_pages)
+                                sample, prefill_chunk, kv_dtype, return_logprobs, kv_page, kv_pool_pages,
+                                weight_dtype)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
-    cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype)
+    cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype, weight_dtype=weight_dtype)
     out = [list(map(int, row)) for row in prompt.tolist()]
     lps = [[] for _ in range(B)]          # (logp_model, logp_sampled) per generated id (the "pen" form)
     result = lambda: (out, lps) if return_logprobs else out
@@ -998,7 +1077,7 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
 def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
                      prefill_chunk: int = 0, kv_dtype: Optional[str] = None, return_logprobs: bool = False,
-                     kv_page: int = 0, kv_pool_pages: Optional[int] = None):
+                     kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
     that has filled the cache frozen inside it (``_step_advance_rows``).  With ``kv_page`` the
@@ -1009,7 +1088,7 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     cap = min(model.args.maxlen, max_len or model.args.maxlen)     # total length at which a row stops
     t_max = min(cap, max(lens) + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype, kv_page=kv_page,
-                             kv_pool_pages=kv_pool_pages)
+                             kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype)
     rows = prompt.tolist()
     out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
     lps = [[] for _ in range(B)]

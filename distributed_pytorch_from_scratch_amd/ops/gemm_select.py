@@ -314,6 +314,19 @@ def small_nt(k, x: torch.Tensor, w: torch.Tensor, bias=None, swiglu: bool = Fals
     return gemm_nt(k, k.swiglu_fwd(x) if swiglu else x, w, bias)
 
 
+def small_nt_w8(k, x: torch.Tensor, w8, bias=None, swiglu: bool = False) -> Optional[torch.Tensor]:
+    """``small_nt`` on fp8 weights, M <= 64 rows: ``w8`` = (codes uint8 [N, K], inv fp32 [N]) of
+    ``_quant_w8_rows``; y = (a codes^T) * inv (+ bias) on gemv_w8_k (csrc/kernels/gemv_w8.hip).
+    None where the kernel does not take the shape (K % 64, strides) or the library backend is
+    pinned: the caller keeps its bf16 route for that projection."""
+    codes, inv = w8
+    if _direct(k) or not x.is_cuda:
+        return k._gemv_nt_w8(x, codes, inv, bias, swiglu)
+    if mode() != "blas" and k._gemv_nt_w8_ok(x, codes, swiglu):
+        return k._gemv_nt_w8(x, codes, inv, bias, swiglu)
+    return None
+
+
 def gemm_nn(k, a: torch.Tensor, b: torch.Tensor, out=None) -> torch.Tensor:
     """c[M,N] = a[M,K] b[K,N] in a.dtype (into ``out`` when given)."""
     fw = F8.lookup(b, dgrad=True)

@@ -454,6 +454,34 @@ def gemv_nt(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = Non
     return y.to(x.dtype)
 
 
+def _quant_w8_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Weight-only fp8: a weight ``[N, K]`` -> (codes uint8 ``[N, K]``, inv fp32 ``[N]``), the row
+    format of ``_kv_quant_rows`` with one row per output channel; the weight is
+    ``f32(e4m3fn(code)) * inv[n]``."""
+    codes, inv = _kv_quant_rows(w)
+    return codes.view(torch.uint8).contiguous(), inv
+
+
+def _gemv_nt_w8_ok(x: torch.Tensor, codes: torch.Tensor, swiglu: bool = False) -> bool:
+    return True
+
+
+def _gemv_nt_w8(x: torch.Tensor, codes: torch.Tensor, inv: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                swiglu: bool = False) -> torch.Tensor:
+    """``gemv_nt`` on fp8 weights: y = (a f32(codes)^T) * inv (+ bias) in x.dtype; the codes are
+    multiplied as they are and the scale is applied once per output column."""
+    if swiglu:
+        K = codes.size(1)
+        g, u = x[:, :K].float(), x[:, K:].float()
+        a = (g / (1.0 + torch.exp(-g)) * u).to(x.dtype)
+    else:
+        a = x
+    y = (a.float() @ codes.view(torch.float8_e4m3fn).float().t()) * inv
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
 def rope_append(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, len: torch.Tensor) -> None:
     """rope_ on the q and k heads of the packed rows, then kv_append (one GPU kernel)."""

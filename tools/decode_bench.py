@@ -9,6 +9,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
                                  [--kv-dtype {act,fp8,both}] [--modes graph eager]
                                  [--penalties R,P,F] [--logprobs]
                                  [--ragged --kv-page N [N ...]]
+                                 [--weight-dtype {act,fp8,both}] [--layers N] [--w8-kernel]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -51,6 +52,14 @@ call with the penalties / log-probabilities, and the lines of the latter carry `
 ``--ragged --kv-page N [N ...]`` decodes the ragged batch with the paged KV cache
 (``generate(..., kv_page=N)``) at every N next to the contiguous per-row cache, in the same
 process and interleaved rounds, and then times the decode-attention launch alone (``paged_bench``).
+
+``--weight-dtype fp8`` decodes with fp8 projection weights (``generate(..., weight_dtype="fp8")``);
+``both`` runs the bf16 and the fp8 weights in interleaved rounds (``--repeats`` of them, each
+session warm; ``w8_bench``) with the median and spread per (batch, mode, weights) and whether the
+tokens agree.  ``--layers N`` builds the preset with N layers (a large preset inside a short run).
+``--w8-kernel`` times the projection launch alone on the preset's QKV, Wo, gate|up, down and
+lm_head shapes: ``_gemv_nt_w8`` against ``gemv_nt`` (M <= 16) or the ``gemm_nt`` route (M > 16), 100
+launches per graph replay, with weight bytes / time (``w8_kernel_bench``).
 """
 from __future__ import annotations
 
@@ -93,6 +102,10 @@ def main():
     ap.add_argument("--logprobs", action="store_true", help="the penalised form returns log-probabilities")
     ap.add_argument("--kv-page", type=int, nargs="+", default=None, metavar="N",
                     help="--ragged: the paged KV cache at these page sizes next to the contiguous one")
+    ap.add_argument("--weight-dtype", choices=["act", "fp8", "both"], default="act",
+                    help="projection weights of the decode steps: bf16, fp8 codes, or both in interleaved rounds")
+    ap.add_argument("--layers", type=int, default=0, help="build the preset with this many layers (0: its own)")
+    ap.add_argument("--w8-kernel", action="store_true", help="time the fp8-weight projection launch alone")
     a = ap.parse_args()
     if a.kv_page and not a.ragged:
         ap.error("--kv-page runs the ragged decode benchmark: give --ragged")
@@ -123,7 +136,9 @@ def main():
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29591")
     init_dist_env(rank=0, tp_size=1, world_size=1)
-    args = get_preset(a.model)
+    args = get_preset(a.model, **({"num_layers": a.layers} if a.layers else {}))
+    if a.w8_kernel:
+        return w8_kernel_bench(a, args)
     if a.continuation and a.t0 + a.chunk > args.maxlen:     # the RoPE table must cover the continuation
         args = get_preset(a.model, maxlen=a.t0 + a.chunk)
     m = Transformer.from_args(args).cuda()
@@ -137,6 +152,8 @@ def main():
         return prefill_bench(a, m)
     if a.kv_page:
         return paged_bench(a, m)
+    if a.weight_dtype != "act":
+        return w8_bench(a, m)
     for B in a.batch:
         prompt = torch.randint(0, args.vocab_size, (B, a.prompt), device="cuda")
         lens = None
@@ -324,6 +341,95 @@ def paged_bench(a, m):
                               "heads": H, "head_dim": hd, "t_max": t_max, "kv_page": p, "us_per_call": us[p],
                               "us_per_call_median": _median(us[p]),
                               "us_per_call_spread": round(max(us[p]) - min(us[p]), 2)}), flush=True)
+
+
+def w8_bench(a, m):
+    """``--weight-dtype``: the greedy decode of ``main`` with bf16 and / or fp8 projection weights in
+    one process and interleaved rounds (every session warm); one line per (batch, mode, weights)."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.models import generation as G
+    wds = {"fp8": ["fp8"], "both": [None, "fp8"]}[a.weight_dtype]
+    kd = None if a.kv_dtype == "act" else "fp8"
+    for B in a.batch:
+        prompt = torch.randint(0, m.args.vocab_size, (B, a.prompt), device="cuda")
+        for mode in a.modes:
+            os.environ["DPFS_DECODE_GRAPH"] = "1" if mode == "graph" else "0"
+            run = lambda wd: G.generate(m, prompt, max_new_tokens=a.new, kv_dtype=kd, weight_dtype=wd)
+            toks = {wd: run(wd) for wd in wds}                      # warm-up: GEMM choices, graph capture
+            ms = {wd: [] for wd in wds}
+            for _ in range(a.repeats):
+                for wd in wds:                                      # interleaved rounds
+                    ms[wd].append(round(_timed(lambda: run(wd)) / a.new, 4))
+            agree = None
+            if None in toks:    # generated ids equal to the bf16 weights' (quantisation may change an argmax)
+                agree = sum(x == y for r, q in zip(toks[None], toks["fp8"]) for x, y in zip(r, q)) / (B * len(toks[None][0]))
+            for wd in wds:
+                print(json.dumps({"bench": "weight_dtype", "model": a.model, "layers": len(m.layers), "batch": B,
+                                  "mode": mode, "prompt": a.prompt, "new": a.new, "kv_dtype": kd or "act",
+                                  "weight_dtype": wd or "act", "ms_per_step": ms[wd],
+                                  "ms_per_step_median": _median(ms[wd]),
+                                  "ms_per_step_spread": round(max(ms[wd]) - min(ms[wd]), 4),
+                                  "tokens_per_s_median": round(B / _median(ms[wd]) * 1000, 1),
+                                  "token_agreement_with_act": agree if wd else None}), flush=True)
+        G.clear_sessions()
+
+
+PEAK_HBM_TBS = 8.0     # MI355X HBM3E peak, TB/s: the floor of a launch is its weight bytes at this rate
+
+
+def w8_kernel_bench(a, args):
+    """``--w8-kernel``: us per projection launch on the preset's shapes at every ``--batch`` M."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.ops import _ext
+    from distributed_pytorch_from_scratch_amd.ops import gemm_select as GS
+    C = _ext.require()
+    d, f, v = args.attn_dim, args.ffn_dim, (args.vocab_size + 127) // 128 * 128
+    shapes = [("qkv", 3 * d, d, False), ("wo", d, d, False), ("gate_up", 2 * f, d, False), ("down", d, f, True),
+              ("lm_head", v, d, False)]
+    for name, N, K, sw in shapes:
+        # the 100 launches of a replay walk over copies of the weight that together exceed the 256 MB
+        # infinity cache (600 MB of codes), so every launch streams its weight from HBM as a decode
+        # step of a model larger than the cache does
+        nc = min(100, -(-600 * 2 ** 20 // (N * K)))
+        ws = [(torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16() for _ in range(nc)]
+        qs = [C._quant_w8_rows(w) for w in ws]
+        for M in a.batch:
+            x = torch.randn(M, 2 * K if sw else K, device="cuda").bfloat16()
+            ref = "gemv_nt" if M <= 16 else "gemm_nt"
+            launch = {"w8": lambda i: C._gemv_nt_w8(x, qs[i % nc][0], qs[i % nc][1], None, sw),
+                      ref: (lambda i: C.gemv_nt(x, ws[i % nc], None, sw)) if M <= 16 else
+                           (lambda i: GS.gemm_nt(C, C.swiglu_fwd(x) if sw else x, ws[i % nc]))}
+            graphs = {}
+            for k_, fn in launch.items():
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for i in range(3):
+                        fn(i)
+                torch.cuda.current_stream().wait_stream(s)
+                graphs[k_] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[k_]):
+                    for i in range(100):
+                        fn(i)
+                graphs[k_].replay()
+            us = {k_: [] for k_ in launch}
+            for _ in range(max(a.repeats, 5)):
+                for k_, g in graphs.items():                        # interleaved rounds
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[k_].append(round(10 * e0.elapsed_time(e1), 2))
+            for k_ in launch:
+                wbytes = N * K * (1 if k_ == "w8" else 2) + (4 * N if k_ == "w8" else 0)
+                med = _median(us[k_])
+                floor = wbytes / (PEAK_HBM_TBS * 1e6)
+                print(json.dumps({"bench": "w8_kernel", "model": a.model, "proj": name, "M": M, "N": N, "K": K,
+                                  "kernel": k_, "weight_copies": nc, "us_per_call": us[k_], "us_per_call_median": med,
+                                  "us_per_call_spread": round(max(us[k_]) - min(us[k_]), 2), "weight_bytes": wbytes,
+                                  "weight_TBps": round(wbytes / med / 1e6, 3), "floor_us_at_peak": round(floor, 2),
+                                  "share_of_peak": round(floor / med, 3)}), flush=True)
 
 
 def prefill_bench(a, m):
