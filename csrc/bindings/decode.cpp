@@ -188,6 +188,60 @@ std::vector<torch::Tensor> quant_w8_rows(torch::Tensor w) {
   return {codes, inv};
 }
 
+// ----------------------------------------------------------------- MXFP4 weights (decode) --
+// Weight-only MXFP4 projections (kernels/gemv_w4.hip): e2m1 codes uint8 [N, K / 2] (low nibble first)
+// with one e8m0 scale per 32 k, uint8 [N, K / 32]; value = e2m1(code) * 2^(s - 127).  Bound with
+// leading underscores, as the fp8 ones.
+bool gemv_nt_w4_ok(torch::Tensor x, torch::Tensor codes, bool swiglu) {
+  if (!x.is_cuda() || !codes.is_cuda() || x.dim() != 2 || codes.dim() != 2 || x.scalar_type() != torch::kBFloat16 ||
+      codes.scalar_type() != torch::kUInt8 || x.stride(1) != 1 || codes.stride(1) != 1 || x.device() != codes.device())
+    return false;
+  const int64_t K = 2 * codes.size(1);
+  if (x.size(1) != (swiglu ? 2 * K : K) || codes.size(0) >= (1LL << 31) || K >= (1LL << 31)) return false;
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 || reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16)
+    return false;   // 16-byte operand loads
+  return dpfs_gemv_w4_ok((int)x.size(0), (int)codes.size(0), (int)K, x.stride(0), codes.stride(0), K / 32) != 0;
+}
+
+// y[M, N] = bf16(a wq^T + bias) for M <= 64, a = x or with swiglu silu(gate) * up of the packed
+// x = [gate | up]; fp32 accumulation, the block scales inside wq: no scale in the epilogue.
+torch::Tensor gemv_nt_w4(torch::Tensor x, torch::Tensor codes, torch::Tensor scales,
+                         c10::optional<torch::Tensor> bias, bool swiglu) {
+  TORCH_CHECK(gemv_nt_w4_ok(x, codes, swiglu),
+              "gemv_nt_w4: needs bf16 row-major x [M <= 64, K or 2K] (row stride % 8 == 0) and uint8 codes [N, K / 2] "
+              "(row stride % 16 == 0) on one device, both 16-byte aligned, K % 128 == 0");
+  const int64_t M = x.size(0), N = codes.size(0), K = 2 * codes.size(1);
+  TORCH_CHECK(scales.is_cuda() && scales.device() == x.device() && scales.scalar_type() == torch::kUInt8 &&
+                  scales.dim() == 2 && scales.size(0) == N && scales.size(1) == K / 32 && scales.stride(1) == 1 &&
+                  scales.stride(0) % 4 == 0 && scales.stride(0) >= K / 32 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "gemv_nt_w4: scales must be a 4-byte aligned uint8 [N, K / 32] on x's device with a row stride % 4 == 0");
+  const at::DeviceGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  dpfs_gemv_w4(x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0),
+               opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M, (int)N, (int)K, swiglu ? 1 : 0, stream());
+  return y;
+}
+
+// (codes uint8 [N, K / 2], scales uint8 [N, K / 32]) of a bf16 weight [N, K], K % 128 == 0: the OCP MX
+// conversion, the bytes of ops/reference.py:_quant_w4_rows.
+std::vector<torch::Tensor> quant_w4_rows(torch::Tensor w) {
+  check_cuda(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == torch::kBFloat16 && w.stride(1) == 1 && w.size(1) % 128 == 0 &&
+                  w.size(1) > 0 && (w.size(0) <= 1 || (w.stride(0) % 8 == 0 && w.stride(0) >= w.size(1))) &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && w.size(0) < (1LL << 31) &&
+                  w.size(1) < (1LL << 31),
+              "quant_w4_rows: w must be a 16-byte aligned bf16 [N, K] with unit column stride, K % 128 == 0 and a row "
+              "stride % 8 == 0");
+  const int64_t N = w.size(0), K = w.size(1);
+  const at::DeviceGuard g(w.device());
+  auto codes = torch::empty({N, K / 2}, w.options().dtype(torch::kUInt8));
+  auto scales = torch::empty({N, K / 32}, w.options().dtype(torch::kUInt8));
+  dpfs_quant_w4_rows(w.data_ptr(), w.stride(0), codes.data_ptr(), K / 2, scales.data_ptr(), K / 32, (int)N, (int)K,
+                     stream());
+  return {codes, scales};
+}
+
 // rope_ on the q and k heads of the packed qkv rows + kv_append of the rotated k and v rows
 // at *len, one kernel (decode step).
 void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kc, torch::Tensor vc,
@@ -720,6 +774,10 @@ void bind_decode(py::module_& m) {
   m.def("_gemv_nt_w8", &gemv_nt_w8, py::arg("x"), py::arg("codes"), py::arg("inv"), py::arg("bias") = py::none(),
         py::arg("swiglu") = false);
   m.def("_quant_w8_rows", &quant_w8_rows, py::arg("w"));
+  m.def("_gemv_nt_w4_ok", &gemv_nt_w4_ok, py::arg("x"), py::arg("codes"), py::arg("swiglu") = false);
+  m.def("_gemv_nt_w4", &gemv_nt_w4, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none(),
+        py::arg("swiglu") = false);
+  m.def("_quant_w4_rows", &quant_w4_rows, py::arg("w"));
   m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("len"));
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),

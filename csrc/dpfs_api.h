@@ -244,6 +244,16 @@ int dpfs_gemm_tn_group(int n, const void* const* A, const void* const* B, float*
                        const void* const* A2, const void* const* B2, const int* lda2, const int* ldb2, int K1,
                        hipStream_t s);
 
+// kernels/gemv_w4.hip
+// weight-only MXFP4 decode projections: e2m1 codes [N, K / 2] (row stride ldc bytes, low nibble
+// first) with e8m0 scales [N, K / 32] (row stride lds bytes), K % 128 == 0
+int dpfs_gemv_w4_ok(int M, int N, int K, long long lda, long long ldc, long long lds);
+void dpfs_gemv_w4(const void* A, long long lda, const void* codes, long long ldc, const void* scales,
+                  long long lds, const float* bias, void* Y, long long ldy, int M, int N, int K, int swiglu,
+                  hipStream_t s);
+void dpfs_quant_w4_rows(const void* W, long long ldw, void* codes, long long ldc, void* scales, long long lds,
+                        int N, int K, hipStream_t s);
+
 // kernels/gemv_w8.hip
 // weight-only fp8 decode projections: e4m3 codes [N, K] (row stride ldc bytes) with fp32 inv [N]
 int dpfs_gemv_w8_ok(int M, int N, int K, long long lda, long long ldc);

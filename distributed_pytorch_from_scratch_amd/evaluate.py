@@ -93,9 +93,10 @@ def get_test_args(argv=None):
                    help="prefill a prompt in pieces of at most this many tokens (0: whole)")
     g.add_argument("--kv_cache_dtype", choices=["act", "fp8"], default="act",
                    help="KV cache storage: the activation dtype, or e4m3 codes with per-row fp32 scales")
-    g.add_argument("--weight_dtype", choices=["act", "fp8"], default="act",
-                   help="projection weights of the one-token decode steps: the activation dtype, or e4m3 codes "
-                        "with one fp32 scale per output channel (KV-cached decoding; the prefill keeps bf16)")
+    g.add_argument("--weight_dtype", choices=["act", "fp8", "mxfp4"], default="act",
+                   help="projection weights of the one-token decode steps: the activation dtype, e4m3 codes "
+                        "with one fp32 scale per output channel, or OCP MXFP4 (e2m1 codes, one e8m0 scale per "
+                        "32 k) (KV-cached decoding; the prefill keeps bf16)")
     g.add_argument("--kv_page", type=int, default=0,
                    help="keep the KV cache in pages of this many tokens (a power of two in [16, 256]; 0: contiguous)")
     g.add_argument("--kv_pool_pages", type=int, default=0,

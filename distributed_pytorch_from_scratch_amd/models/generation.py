@@ -63,6 +63,10 @@ csrc/kernels/gemv_w8.hip), quantised once per session and kept on its cache (``c
 prefill and the extend pieces keep the bf16 weights: they are compute-bound, only the one-token
 steps are bound by the weight bytes.
 
+MXFP4 weights (``weight_dtype="mxfp4"``): the same projections on OCP MX codes, e2m1 elements with one
+e8m0 scale per 32 consecutive k (``_quant_w4_rows``; ``_gemv_nt_w4``, csrc/kernels/gemv_w4.hip: 0.53
+bytes per parameter), under the rules of the fp8 weights and kept as ``cache.w4``.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -96,6 +100,7 @@ class KVCache:
 
     page = 0    # the page size of a ``PagedKVCache``; 0: this contiguous form
     w8 = None   # fp8 decode weights of the session (``quantise_weights``); None: bf16 weights
+    w4 = None   # MXFP4 decode weights of the session (``quantise_weights``); None: bf16 or fp8 weights
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
                  ragged: bool = False, kv_dtype: Optional[str] = None):
@@ -346,30 +351,35 @@ class SamplePen(SampleRows):
         return self
 
 
-W8_MAX_BATCH = 64     # rows of the fp8-weight projection kernel (gemv_w8_k: four 16-row MFMA tiles)
+W8_MAX_BATCH = 64     # rows of the quantised-weight projection kernels (gemv_w8_k, gemv_w4_k: four 16-row MFMA tiles)
+WEIGHT_DTYPES = {"fp8": 64, "mxfp4": 128}     # weight_dtype -> the K multiple its kernel takes
 
 
 def _check_weight_dtype(model, B: int, weight_dtype, who: str = "generate") -> None:
-    if weight_dtype not in (None, "fp8"):
-        raise ValueError(f"{who}: weight_dtype must be None (the activation dtype) or 'fp8', got {weight_dtype!r}")
     if weight_dtype is None:
         return
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"{who}: weight_dtype must be None (the activation dtype), 'fp8' or 'mxfp4', got "
+                         f"{weight_dtype!r}")
     if B > W8_MAX_BATCH:
-        raise ValueError(f"{who}: weight_dtype='fp8' decodes at most {W8_MAX_BATCH} sequences per batch, got {B}")
+        raise ValueError(f"{who}: weight_dtype={weight_dtype!r} decodes at most {W8_MAX_BATCH} sequences per batch, "
+                         f"got {B}")
     if model.args.norm != "rmsnorm":
-        raise ValueError(f"{who}: weight_dtype='fp8' needs the RMSNorm model (norm={model.args.norm!r} decodes "
-                         "through the module layers, which keep their own weights)")
+        raise ValueError(f"{who}: weight_dtype={weight_dtype!r} needs the RMSNorm model (norm={model.args.norm!r} "
+                         "decodes through the module layers, which keep their own weights)")
     if model.compute_dtype == torch.float32:
-        raise ValueError(f"{who}: weight_dtype='fp8' needs bf16 compute (the codes feed bf16 MFMAs), the model is "
-                         "set to fp32 compute")
+        raise ValueError(f"{who}: weight_dtype={weight_dtype!r} needs bf16 compute (the codes feed bf16 MFMAs), the "
+                         "model is set to fp32 compute")
 
 
-def quantise_weights(model, dev) -> dict:
+def quantise_weights(model, dev, weight_dtype: str = "fp8") -> dict:
     """The projection weights of the decode step (QKV, Wo, gate|up, down of every layer and the
     lm_head; under TP this rank's shards) as weight-only fp8: ``{id(parameter): (codes uint8
     [N, K], inv fp32 [N])}``, one scale per output row (``ops/reference.py:_quant_w8_rows``),
     quantised from the compute copy of the parameter by ``_quant_w8_rows``.  A weight whose K is
-    not a multiple of 64 is left out: its projection keeps the bf16 route."""
+    not a multiple of 64 is left out: its projection keeps the bf16 route.  ``weight_dtype="mxfp4"``:
+    ``(codes uint8 [N, K/2], scales uint8 [N, K/32])`` of ``_quant_w4_rows``, one e8m0 scale per 32 k;
+    a weight whose K is not a multiple of 128 is left out."""
     from .engine_common import _Layer
     dev = torch.device(dev)
     dt = model.act_dtype(dev)
@@ -378,7 +388,8 @@ def quantise_weights(model, dev) -> dict:
     for layer in model.layers:
         L = _Layer(layer)
         ws += [L.wqkv, L.wo, L.wgu, L.wd]
-    return {id(w): tuple(k._quant_w8_rows(shadow(w, dt))) for w in ws if w.size(1) % 64 == 0}
+    quant = k._quant_w4_rows if weight_dtype == "mxfp4" else k._quant_w8_rows
+    return {id(w): tuple(quant(shadow(w, dt))) for w in ws if w.size(1) % WEIGHT_DTYPES[weight_dtype] == 0}
 
 
 def _penalty_settings(B: int, repetition_penalty, presence_penalty, frequency_penalty):
@@ -636,8 +647,8 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     host state: graph-capturable."""
     from .engine_common import _Layer
     if model.args.norm != "rmsnorm":
-        if cache.w8 is not None:
-            raise ValueError("decode_step: fp8 weights need the RMSNorm model")
+        if cache.w8 is not None or cache.w4 is not None:
+            raise ValueError("decode_step: fp8 and MXFP4 weights need the RMSNorm model")
         return _decode_step_modules(model, ids, pos, cache, sample)
     B = ids.size(0)
     dev = ids.device
@@ -649,16 +660,17 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     tab = model.rope_table(dev)
     pend = pend_bias = None
     small = B <= 16
-    w8 = cache.w8 or {}
+    wq, small_q = (cache.w4, GS.small_nt_w4) if cache.w4 is not None else (cache.w8 or {}, GS.small_nt_w8)
 
     def proj(a, w, bias=None, swiglu=False):
         # fp8 weights (cache.w8, B <= 64): gemv_w8_k on the session's codes of this parameter.  A
         # projection without codes (K % 64 != 0) or whose operands the kernel declines (a pinned
         # library backend) keeps the bf16 route below; with d, the local head width and the local
-        # ffn width all multiples of 64 no projection falls back.
-        q = w8.get(id(w))
+        # ffn width all multiples of 64 no projection falls back.  MXFP4 weights (cache.w4): the
+        # same on gemv_w4_k, with 128 for 64.
+        q = wq.get(id(w))
         if q is not None:
-            y = GS.small_nt_w8(k, a, q, bias, swiglu)
+            y = small_q(k, a, q, bias, swiglu)
             if y is not None:
                 return y
         w = W(w)
@@ -842,7 +854,8 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     pools and table) are kept; ``clear_sessions()`` frees them.  A paged cache (``kv_page`` > 0) is
     a form of the cache like its dtype: its key is the unpaged key followed by (kv_page,
     kv_pool_pages), and the paged sessions of the kept shape stay beside the unpaged ones.  fp8 weights
-    (``weight_dtype="fp8"``) are a form of the session too: the key ends in ("weights", "fp8"),
+    (``weight_dtype="fp8"``; ``"mxfp4"`` likewise, as ``cache.w4``) are a form of the session too: the key
+    ends in ("weights", "fp8"),
     behind everything the shape comparison below indexes; the codes (``quantise_weights``) hang on
     the session's cache as ``cache.w8``, its graphs replay them, and like the graphs they are
     rebuilt with the session when any parameter's version moves."""
@@ -865,6 +878,8 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
                         ragged, kv_dtype)
     if weight_dtype == "fp8":
         cache.w8 = quantise_weights(model, dev)
+    elif weight_dtype == "mxfp4":
+        cache.w4 = quantise_weights(model, dev, "mxfp4")
     graphs = {}
     kv_bytes = cache.nbytes()             # the fp8 form: codes and scales; the paged form: pools and table
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
@@ -977,7 +992,11 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     ``kv_page``, ``prompt_lens``, ``prefill_chunk``, every sampling form and TP > 1 (each rank
     quantises its own shard; a row-parallel partial sum is scaled before the all-reduce).
     ``ValueError`` for a batch above 64, the LayerNorm model and fp32 compute.  On the CPU the
-    oracle ops run.  ``None``, the default, is every path above unchanged."""
+    oracle ops run.  ``weight_dtype="mxfp4"`` runs the same projections on OCP MXFP4 codes: e2m1
+    elements with one e8m0 scale per 32 consecutive k (``_quant_w4_rows``, round to nearest;
+    ``_gemv_nt_w4``, csrc/kernels/gemv_w4.hip: a quarter of the bf16 weight bytes plus the scales),
+    under the same rules with 128 for 64; its row-parallel partial sums need no scale.  ``None``,
+    the default, is every path above unchanged."""
     _check_weight_dtype(model, prompt.size(0), weight_dtype)
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")

@@ -327,6 +327,19 @@ def small_nt_w8(k, x: torch.Tensor, w8, bias=None, swiglu: bool = False) -> Opti
     return None
 
 
+def small_nt_w4(k, x: torch.Tensor, w4, bias=None, swiglu: bool = False) -> Optional[torch.Tensor]:
+    """``small_nt`` on MXFP4 weights, M <= 64 rows: ``w4`` = (codes uint8 [N, K/2], scales uint8
+    [N, K/32]) of ``_quant_w4_rows``; y = a wq^T (+ bias) on gemv_w4_k (csrc/kernels/gemv_w4.hip).
+    None where the kernel does not take the shape (K % 128, strides) or the library backend is
+    pinned: the caller keeps its bf16 route for that projection."""
+    codes, scales = w4
+    if _direct(k) or not x.is_cuda:
+        return k._gemv_nt_w4(x, codes, scales, bias, swiglu)
+    if mode() != "blas" and k._gemv_nt_w4_ok(x, codes, swiglu):
+        return k._gemv_nt_w4(x, codes, scales, bias, swiglu)
+    return None
+
+
 def gemm_nn(k, a: torch.Tensor, b: torch.Tensor, out=None) -> torch.Tensor:
     """c[M,N] = a[M,K] b[K,N] in a.dtype (into ``out`` when given)."""
     fw = F8.lookup(b, dgrad=True)

@@ -482,6 +482,51 @@ def _gemv_nt_w8(x: torch.Tensor, codes: torch.Tensor, inv: torch.Tensor, bias: O
     return y.to(x.dtype)
 
 
+def _quant_w4_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Weight-only MXFP4 (OCP MX v1.0): a weight ``[N, K]``, K % 128 == 0 -> (codes uint8
+    ``[N, K/2]``, scales uint8 ``[N, K/32]``).  Element k of row n sits in bits ``4 (k % 2) .. +3`` of
+    byte ``k / 2`` (low nibble first) as sign + e2m1 (magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6); scale
+    byte s of block ``k / 32`` means ``2^(s - 127)``.  Per block, E = the biased exponent field of
+    max|w|, s = max(E - 2, 2) (the floor keeps every dequantised value a normal bf16), q = w
+    ``2^(127 - s)``, the code the nearest e2m1 magnitude, ties to the even code, saturating at 6.
+    Written on the bits of the bf16 weight with integer operations, the ones of quant_w4_rows_k
+    (csrc/kernels/gemv_w4.hip): |w| = mant ``2^(e' - 134)``, so in units of 0.25 q = mant ``2^-t``
+    with t = s + 5 - e' >= 3, and the code counts the grid's midpoints (1, 3, 5, 7, 10, 14, 20
+    quarter units) below q.  Non-finite weights are outside the contract."""
+    N, K = w.shape
+    assert K % 128 == 0, "MXFP4 weights need K % 128 == 0"
+    b = w.detach().to(torch.bfloat16).contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    mag = b & 0x7FFF
+    s = ((mag.view(N, K // 32, 32).amax(-1) >> 7) - 2).clamp_min(2)
+    e = mag >> 7
+    mant = (mag & 0x7F) | ((e > 0).to(torch.int32) << 7)
+    t = (s.repeat_interleave(32, 1) + 5 - e.clamp_min(1)).clamp_max(24)
+    q, f = mant << (24 - t), 1 << 24
+    code = ((q > f).to(torch.int32) + (q >= 3 * f) + (q > 5 * f) + (q >= 7 * f) + (q > 10 * f) + (q >= 14 * f)
+            + (q > 20 * f)) | ((b >> 12) & 8)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8), s.to(torch.uint8)
+
+
+def _dequant_w4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 ``[N, K]`` of MXFP4 codes and scales: e2m1(code) * 2^(s - 127), each a bf16 value for
+    s >= 2."""
+    mags = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], device=codes.device)
+    nib = torch.stack((codes & 15, codes >> 4), -1).flatten(1).long()
+    v = torch.where(nib >= 8, -mags[nib & 7], mags[nib & 7])
+    return v * (scales.to(torch.int32) << 23).view(torch.float32).repeat_interleave(32, 1)
+
+
+def _gemv_nt_w4_ok(x: torch.Tensor, codes: torch.Tensor, swiglu: bool = False) -> bool:
+    return True
+
+
+def _gemv_nt_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                swiglu: bool = False) -> torch.Tensor:
+    """``gemv_nt`` on MXFP4 weights: y = a wq^T (+ bias) in x.dtype with wq = e2m1(code) *
+    2^(s - 127); the block scales are inside wq, the epilogue has no scale multiply."""
+    return gemv_nt(x, _dequant_w4(codes, scales), bias, swiglu)
+
+
 def rope_append(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, len: torch.Tensor) -> None:
     """rope_ on the q and k heads of the packed rows, then kv_append (one GPU kernel)."""

@@ -36,8 +36,10 @@ ARCH = os.environ.get("DPFS_OFFLOAD_ARCH", "gfx950")
 # (its long-lived ones are asm-owned AGPRs, csrc/kernels/attn_acc.inc), so the compiler must
 # not pick the AGPR form for its own MFMAs there; the other kernels keep the default heuristics.
 PER_FILE_FLAGS = {"attention_fused.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-                  # no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in the fp8-weight projections: plain fp32 ops
-                  "gemv_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                  # no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in the fp8- and MXFP4-weight projections:
+                  # plain fp32 ops
+                  "gemv_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                  "gemv_w4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:

@@ -9,7 +9,7 @@ reference's full recompute per token (test.py:144-150), one GPU.
                                  [--kv-dtype {act,fp8,both}] [--modes graph eager]
                                  [--penalties R,P,F] [--logprobs]
                                  [--ragged --kv-page N [N ...]]
-                                 [--weight-dtype {act,fp8,both}] [--layers N] [--w8-kernel]
+                                 [--weight-dtype {act,fp8,mxfp4,both,all}] [--layers N] [--w8-kernel]
 
 Prints one JSON line per (batch, mode): ms per generated token (per step of the batch) and
 tokens/s (batch x steps / time).  ``--temperature`` > 0 decodes with the sampling step
@@ -56,10 +56,11 @@ process and interleaved rounds, and then times the decode-attention launch alone
 ``--weight-dtype fp8`` decodes with fp8 projection weights (``generate(..., weight_dtype="fp8")``);
 ``both`` runs the bf16 and the fp8 weights in interleaved rounds (``--repeats`` of them, each
 session warm; ``w8_bench``) with the median and spread per (batch, mode, weights) and whether the
-tokens agree.  ``--layers N`` builds the preset with N layers (a large preset inside a short run).
+tokens agree; ``mxfp4`` decodes with MXFP4 weights (``weight_dtype="mxfp4"``) and ``all`` runs bf16, fp8
+and MXFP4 in the same rounds.  ``--layers N`` builds the preset with N layers (a large preset inside a short run).
 ``--w8-kernel`` times the projection launch alone on the preset's QKV, Wo, gate|up, down and
-lm_head shapes: ``_gemv_nt_w8`` against ``gemv_nt`` (M <= 16) or the ``gemm_nt`` route (M > 16), 100
-launches per graph replay, with weight bytes / time (``w8_kernel_bench``).
+lm_head shapes: ``_gemv_nt_w8`` and ``_gemv_nt_w4`` against ``gemv_nt`` (M <= 16) or the ``gemm_nt``
+route (M > 16), 100 launches per graph replay, with weight bytes / time (``w8_kernel_bench``).
 """
 from __future__ import annotations
 
@@ -102,10 +103,12 @@ def main():
     ap.add_argument("--logprobs", action="store_true", help="the penalised form returns log-probabilities")
     ap.add_argument("--kv-page", type=int, nargs="+", default=None, metavar="N",
                     help="--ragged: the paged KV cache at these page sizes next to the contiguous one")
-    ap.add_argument("--weight-dtype", choices=["act", "fp8", "both"], default="act",
-                    help="projection weights of the decode steps: bf16, fp8 codes, or both in interleaved rounds")
+    ap.add_argument("--weight-dtype", choices=["act", "fp8", "mxfp4", "both", "all"], default="act",
+                    help="projection weights of the decode steps: bf16, fp8 codes, MXFP4 codes, bf16 and fp8 (both) "
+                         "or all three in interleaved rounds")
     ap.add_argument("--layers", type=int, default=0, help="build the preset with this many layers (0: its own)")
-    ap.add_argument("--w8-kernel", action="store_true", help="time the fp8-weight projection launch alone")
+    ap.add_argument("--w8-kernel", action="store_true",
+                    help="time the fp8- and MXFP4-weight projection launches alone")
     a = ap.parse_args()
     if a.kv_page and not a.ragged:
         ap.error("--kv-page runs the ragged decode benchmark: give --ragged")
@@ -344,11 +347,11 @@ def paged_bench(a, m):
 
 
 def w8_bench(a, m):
-    """``--weight-dtype``: the greedy decode of ``main`` with bf16 and / or fp8 projection weights in
-    one process and interleaved rounds (every session warm); one line per (batch, mode, weights)."""
+    """``--weight-dtype``: the greedy decode of ``main`` with bf16, fp8 and / or MXFP4 projection weights
+    in one process and interleaved rounds (every session warm); one line per (batch, mode, weights)."""
     import torch
     from distributed_pytorch_from_scratch_amd.models import generation as G
-    wds = {"fp8": ["fp8"], "both": [None, "fp8"]}[a.weight_dtype]
+    wds = {"fp8": ["fp8"], "mxfp4": ["mxfp4"], "both": [None, "fp8"], "all": [None, "fp8", "mxfp4"]}[a.weight_dtype]
     kd = None if a.kv_dtype == "act" else "fp8"
     for B in a.batch:
         prompt = torch.randint(0, m.args.vocab_size, (B, a.prompt), device="cuda")
@@ -360,9 +363,9 @@ def w8_bench(a, m):
             for _ in range(a.repeats):
                 for wd in wds:                                      # interleaved rounds
                     ms[wd].append(round(_timed(lambda: run(wd)) / a.new, 4))
-            agree = None
-            if None in toks:    # generated ids equal to the bf16 weights' (quantisation may change an argmax)
-                agree = sum(x == y for r, q in zip(toks[None], toks["fp8"]) for x, y in zip(r, q)) / (B * len(toks[None][0]))
+            # generated ids equal to the bf16 weights' (quantisation may change an argmax)
+            agree = {wd: sum(x == y for r, q in zip(toks[None], toks[wd]) for x, y in zip(r, q)) / (B * len(toks[None][0]))
+                     for wd in wds if wd and None in toks}
             for wd in wds:
                 print(json.dumps({"bench": "weight_dtype", "model": a.model, "layers": len(m.layers), "batch": B,
                                   "mode": mode, "prompt": a.prompt, "new": a.new, "kv_dtype": kd or "act",
@@ -370,7 +373,7 @@ def w8_bench(a, m):
                                   "ms_per_step_median": _median(ms[wd]),
                                   "ms_per_step_spread": round(max(ms[wd]) - min(ms[wd]), 4),
                                   "tokens_per_s_median": round(B / _median(ms[wd]) * 1000, 1),
-                                  "token_agreement_with_act": agree if wd else None}), flush=True)
+                                  "token_agreement_with_act": agree.get(wd)}), flush=True)
         G.clear_sessions()
 
 
@@ -393,12 +396,15 @@ def w8_kernel_bench(a, args):
         nc = min(100, -(-600 * 2 ** 20 // (N * K)))
         ws = [(torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16() for _ in range(nc)]
         qs = [C._quant_w8_rows(w) for w in ws]
+        q4 = [C._quant_w4_rows(w) for w in ws] if K % 128 == 0 else None
         for M in a.batch:
             x = torch.randn(M, 2 * K if sw else K, device="cuda").bfloat16()
             ref = "gemv_nt" if M <= 16 else "gemm_nt"
             launch = {"w8": lambda i: C._gemv_nt_w8(x, qs[i % nc][0], qs[i % nc][1], None, sw),
                       ref: (lambda i: C.gemv_nt(x, ws[i % nc], None, sw)) if M <= 16 else
                            (lambda i: GS.gemm_nt(C, C.swiglu_fwd(x) if sw else x, ws[i % nc]))}
+            if q4:
+                launch["w4"] = lambda i: C._gemv_nt_w4(x, q4[i % nc][0], q4[i % nc][1], None, sw)
             graphs = {}
             for k_, fn in launch.items():
                 s = torch.cuda.Stream()
@@ -422,7 +428,7 @@ def w8_kernel_bench(a, args):
                     torch.cuda.synchronize()
                     us[k_].append(round(10 * e0.elapsed_time(e1), 2))
             for k_ in launch:
-                wbytes = N * K * (1 if k_ == "w8" else 2) + (4 * N if k_ == "w8" else 0)
+                wbytes = {"w8": N * K + 4 * N, "w4": N * K // 2 + N * K // 32}.get(k_, 2 * N * K)
                 med = _median(us[k_])
                 floor = wbytes / (PEAK_HBM_TBS * 1e6)
                 print(json.dumps({"bench": "w8_kernel", "model": a.model, "proj": name, "M": M, "N": N, "K": K,
