@@ -50,8 +50,19 @@ def test_attn_decode_bounds(C, hd, Tmax, fam):
     as the head of the packed qkv row and contiguous; flat, near one-hot and rising score rows (the
     row max moves through waves and splits, early waves underflow).  Cache rows past each length
     are NaN: the output must be finite and equal to the run with zeros there."""
-    qkv, kc, vc = N.dec_inputs(hd, Tmax, fam, DEV)
-    B, H = N.DEC_B, N.DEC_H
+    _attn_decode_bounds(C, hd, Tmax, fam, N.DEC_H)
+
+
+@pytest.mark.parametrize("Tmax", N.DEC_TMAX)
+def test_attn_decode_bounds_one_head(C, Tmax):
+    """H = 1 at head_dim 64: the one local head of a tensor-parallel rank (2 heads over 2 ranks, the last
+    ranks of 6 heads over 4); the rising family, whose row max moves through the waves and splits."""
+    _attn_decode_bounds(C, 64, Tmax, "rising", 1)
+
+
+def _attn_decode_bounds(C, hd, Tmax, fam, H):
+    qkv, kc, vc = N.dec_inputs(hd, Tmax, fam, DEV, H=H)
+    B = N.DEC_B
     scale = hd ** -0.5
     qc = qkv[:, : H * hd].contiguous()
     lens = N.dec_lengths(Tmax)
@@ -152,7 +163,18 @@ def test_rope_append_head_dim_32(C, lens):
     """rope_append at head_dim 32 (two 8-pair groups per head) == rope_ + kv_append bit for bit,
     uniform and per-row; a full cache (300) is rotated and appends nothing.  With the rope_ bound
     of test_kernel_bounds_gpu this bounds it."""
-    hd, H, Tmax = 32, N.DEC_H, 300
+    _rope_append(C, 32, N.DEC_H, lens)
+
+
+@pytest.mark.parametrize("lens", [[0], [300], [0, 150, 300]])
+def test_rope_append_one_head(C, lens):
+    """rope_append with H = 1 at head_dim 64, the one local head of a tensor-parallel rank: the same
+    identity and bound."""
+    _rope_append(C, 64, 1, lens)
+
+
+def _rope_append(C, hd, H, lens):
+    Tmax = 300
     B = 3
     g = torch.Generator().manual_seed(61 + len(lens) + lens[0])
     kc = torch.randn(B, Tmax, H, hd, generator=g).bfloat16().to(DEV)
@@ -171,7 +193,7 @@ def test_rope_append_head_dim_32(C, lens):
     ref, rmag = N.ref_rope(qkv.double(), pos, tab, 2 * H, hd)
     unit = N.unit_rope(ref, rmag)
     unit[:, 2 * H * hd:] = 0
-    N.assert_within(a, ref, unit, N.DERIVED, f"rope_append hd 32 len {lens}")
+    N.assert_within(a, ref, unit, N.DERIVED, f"rope_append hd {hd} H {H} len {lens}")
     for bi in range(B):
         L = lens[bi] if len(lens) > 1 else lens[0]
         if L < Tmax:

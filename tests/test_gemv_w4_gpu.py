@@ -43,10 +43,11 @@ def test_every_code_exact_and_in_place(C, M):
 
 # (100, 128): one block per lane, idle K-waves, ragged N; (37, 640): 5 quads over 4 K-waves, 2 / 2 / 1 / 0;
 # (48, 3072): the 8 K-wave form, 3 quads each; (8200, 1024): more than 512 column tiles, the wide-N
-# form, ragged N; (32, 7680): K-waves of 8 quads and one of 4, the full 8-quad batch of M <= 16
+# form, ragged N; (32, 7680): K-waves of 8 quads and one of 4, the full 8-quad batch of M <= 16; (49, 128): the
+# ragged lm_head shard of a tensor-parallel rank (97 ids over 2 ranks): one row in the last column tile
 @pytest.mark.parametrize("bias", [False, True])
 @pytest.mark.parametrize("M", [1, 16, 17, 33, 64])
-@pytest.mark.parametrize("Nn,K", [(100, 128), (37, 640), (48, 3072), (8200, 1024), (32, 7680)])
+@pytest.mark.parametrize("Nn,K", [(100, 128), (37, 640), (48, 3072), (8200, 1024), (32, 7680), (49, 128)])
 def test_gemv_w4_bounds(C, Nn, K, M, bias):
     for sw in (False, True) if (Nn, K) in ((37, 640), (48, 3072)) else (False,):
         x, w, b = N.gemv_inputs(M, Nn, K, sw)

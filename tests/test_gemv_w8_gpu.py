@@ -57,10 +57,12 @@ def test_every_code_exact_and_in_place(C, M):
 
 
 # (100, 64): one pair-step, idle K-waves, ragged N; (37, 576): 9 pair-steps over 4 K-waves; (48, 3072):
-# the 8 K-wave form; (8200, 1024): more than 512 column tiles, the wide-N form, ragged N
+# the 8 K-wave form; (8200, 1024): more than 512 column tiles, the wide-N form, ragged N; the shards of a
+# tensor-parallel rank: (49, 192): the ragged lm_head shard of 97 ids over 2 ranks, 3 pair-steps over 4 K-waves;
+# (192, 64): the K 64 Wo shard of one local head, whole 32-column workgroups, one pair-step and idle K-waves
 @pytest.mark.parametrize("bias", [False, True])
 @pytest.mark.parametrize("M", [1, 16, 17, 33, 64])
-@pytest.mark.parametrize("Nn,K", [(100, 64), (37, 576), (48, 3072), (8200, 1024)])
+@pytest.mark.parametrize("Nn,K", [(100, 64), (37, 576), (48, 3072), (8200, 1024), (49, 192), (192, 64)])
 def test_gemv_w8_bounds(C, Nn, K, M, bias):
     for sw in (False, True) if (Nn, K) in ((37, 576), (48, 3072)) else (False,):
         x, w, b = N.gemv_inputs(M, Nn, K, sw)

@@ -195,10 +195,11 @@ def _plumbing(rank, world):
     from distributed_pytorch_from_scratch_amd.models import generation as G
     m, ids = _tiny_model()
     dev = torch.device("cpu")
-    new = lambda kd, ragged=False: G.KVCache(2, 2, 24, 2, 32, torch.float32, dev, ragged=ragged, kv_dtype=kd)
+    h = m.layers[0].attn.num_local_heads          # 2 at one rank, 1 at two
+    new = lambda kd, ragged=False: G.KVCache(2, 2, 24, h, 32, torch.float32, dev, ragged=ragged, kv_dtype=kd)
     c8 = new("fp8")
-    assert c8.fp8 and c8.k[0].dtype == torch.float8_e4m3fn and c8.ks[0].shape == (2, 24, 2) and len(c8.ks) == 2
-    assert c8.nbytes() == 2 * 2 * 2 * 24 * 2 * (32 + 4)
+    assert c8.fp8 and c8.k[0].dtype == torch.float8_e4m3fn and c8.ks[0].shape == (2, 24, h) and len(c8.ks) == 2
+    assert c8.nbytes() == 2 * 2 * 2 * 24 * h * (32 + 4)
     ca = new(None)
     assert not ca.fp8 and ca.k[0].dtype == torch.float32 and not hasattr(ca, "ks")
     e = {}
@@ -240,10 +241,10 @@ def _plumbing(rank, world):
     # generate: its tokens are the argmax of logits_step on an fp8 cache along the same ids, and
     # the logits error along the generated sequence joins the maximum
     p = ids[:, :7].contiguous()
-    gen = {}
+    gen, tokens = {}, {}
     for name, kw in (("uniform", {}), ("ragged", dict(prompt_lens=LENS))):
         G.clear_sessions()
-        toks = G.generate(m, p, 6, kv_dtype="fp8", **kw)
+        toks = tokens[name] = G.generate(m, p, 6, kv_dtype="fp8", **kw)
         lens = kw.get("prompt_lens", [7, 7])
         gen[name] = [len(t) for t in toks]
         assert all(t[:n] == p[b, :n].tolist() for b, (t, n) in enumerate(zip(toks, lens)))
@@ -272,12 +273,27 @@ def _plumbing(rank, world):
         G.generate(m, p, 2, kv_dtype="e5m2")
     except ValueError as ex:
         errs["generate"] = str(ex)
-    return {"e": e, "e_whole0": e_whole0, "e_ragged0": e_ragged0, "gen": gen, "errs": errs}
+    return {"e": e, "e_whole0": e_whole0, "e_ragged0": e_ragged0, "gen": gen, "errs": errs, "tokens": tokens}
 
 
 @pytest.fixture(scope="module")
 def plumbing():
     return run_distributed(_plumbing, 1)[0]
+
+
+@pytest.fixture(scope="module")
+def plumbing_tp2():
+    return run_distributed(_plumbing, 2)
+
+
+def test_two_ranks_agree(plumbing_tp2, plumbing):
+    """One local head per rank: the worker's own assertions hold on both ranks, and the ranks return the
+    same tokens and, from the same gathered logits, the same errors to the bit."""
+    a, b = plumbing_tp2[0], plumbing_tp2[1]
+    assert a["tokens"] == b["tokens"] and a["gen"] == b["gen"] == plumbing["gen"]
+    assert a["e"] == b["e"] and set(a["e"]) == set(plumbing["e"]) and all(v > 0 for v in a["e"].values())
+    assert a["e_whole0"] == b["e_whole0"] == 0 and a["e_ragged0"] == b["e_ragged0"] == 0
+    assert a["errs"] == b["errs"] == plumbing["errs"]
 
 
 def test_model_logits_error_of_the_fp8_cache(plumbing):

@@ -36,7 +36,7 @@ def _u8(c):
     return c.view(torch.uint8)
 
 
-def _blank_caches(Tmax, hd):
+def _blank_caches(Tmax, hd, H=H):
     k8 = torch.full((B, Tmax, H, hd), SENT, dtype=torch.uint8, device=DEV).view(Q.F8)
     ks = torch.full((B, Tmax, H), NAN, device=DEV)
     return k8, k8.clone(), ks, ks.clone()
@@ -55,13 +55,13 @@ def _strided(x, pad=16, off=8):
     return v
 
 
-def _qkv_rows(T, hd, seed):
+def _qkv_rows(T, hd, seed, H=H):
     """Packed rows [B*T, 3 H hd]: randn, with a zero k row, the tie row and an outlier row."""
     g = torch.Generator().manual_seed(seed + 10 * hd + T)
     qkv = torch.randn(B * T, 3, H, hd, generator=g)
     qkv[0, 1, 0] = 0
-    qkv[0, 2, 1] = Q.tie_row(hd)
-    qkv[B * T - 1, 1, 2] = Q.outlier_row(hd, g)
+    qkv[0, 2, 1 % H] = Q.tie_row(hd)
+    qkv[B * T - 1, 1, 2 % H] = Q.outlier_row(hd, g)
     qkv[B * T - 1, 2, 0] = -Q.tie_row(hd)
     return qkv.view(B * T, 3 * H * hd).bfloat16()
 
@@ -105,14 +105,24 @@ def test_rope_append_q8_exact(C, hd, lens):
     """_rope_append_q8 leaves qkv as rope_append leaves it, and its codes and scales equal rope_
     followed by _kv_append_chunk_q8 at T 1 (which the test above ties to the helper): uniform and
     per-row lengths, one row full, and a full uniform cache, where nothing may be written."""
+    _rope_append_q8_exact(C, hd, lens, H)
+
+
+@pytest.mark.parametrize("lens", [[0], [39], [40], [5, 38], [40, 12]])
+def test_rope_append_q8_exact_one_head(C, lens):
+    """H = 1 at head_dim 64: the one local head of a tensor-parallel rank."""
+    _rope_append_q8_exact(C, 64, lens, 1)
+
+
+def _rope_append_q8_exact(C, hd, lens, H):
     Tmax = 40
     g = torch.Generator().manual_seed(73 + hd + sum(lens))
-    qkv = _qkv_rows(1, hd, 74).to(DEV)
+    qkv = _qkv_rows(1, hd, 74, H).to(DEV)
     pos = torch.randint(0, 512, (B,), generator=g).to(DEV)
     tab = N.rope_table(512, hd).to(DEV)
     ln = _i32(lens)
     a = _strided(qkv)
-    k8, v8, ks, vs = _blank_caches(Tmax, hd)
+    k8, v8, ks, vs = _blank_caches(Tmax, hd, H)
     C._rope_append_q8(a, pos, tab, k8, v8, ks, vs, ln)
     # rope_append on bf16 caches: the same rotation
     r = qkv.clone()
@@ -123,7 +133,7 @@ def test_rope_append_q8_exact(C, hd, lens):
     b_ = qkv.clone()
     C.rope_(b_, pos, tab, 2 * H, hd, False)
     assert torch.equal(a, b_)
-    k8b, v8b, ksb, vsb = _blank_caches(Tmax, hd)
+    k8b, v8b, ksb, vsb = _blank_caches(Tmax, hd, H)
     C._kv_append_chunk_q8(b_, k8b, v8b, ksb, vsb, ln, None)
     assert torch.equal(_u8(k8), _u8(k8b)) and torch.equal(_u8(v8), _u8(v8b))
     assert _same_bits(ks, ksb) and _same_bits(vs, vsb)
@@ -155,7 +165,19 @@ def test_attn_decode_q8_bounds(C, dec_cases, hd, Tmax, fam):
     """The cases of test_decode_bounds_gpu.test_attn_decode_bounds on quantised caches.  Rows past
     each length hold NaN codes and NaN scales: the output must be finite, equal to the run with
     zeros there and to the run with contiguous q, and within the oracle's unit."""
-    qkv, k8, v8, ks, vs = dec_cases[hd, Tmax, fam]
+    _attn_decode_q8_bounds(C, dec_cases[hd, Tmax, fam], hd, Tmax, fam, H)
+
+
+@pytest.mark.parametrize("Tmax", N.DEC_TMAX)
+def test_attn_decode_q8_bounds_one_head(C, Tmax):
+    """H = 1 at head_dim 64, the one local head of a tensor-parallel rank; the rising family."""
+    qkv, kc, vc = N.dec_inputs(64, Tmax, "rising", H=1)
+    (k8, ks), (v8, vs) = Q.quant_cache(kc), Q.quant_cache(vc)
+    _attn_decode_q8_bounds(C, tuple(t.to(DEV) for t in (qkv, k8, v8, ks, vs)), 64, Tmax, "rising", 1)
+
+
+def _attn_decode_q8_bounds(C, case, hd, Tmax, fam, H):
+    qkv, k8, v8, ks, vs = case
     scale = hd ** -0.5
     qc = qkv[:, : H * hd].contiguous()
     lens = N.dec_lengths(Tmax)

@@ -10,6 +10,7 @@ guard page in front and one behind: an index of -1 or P used unchecked lands in 
 """
 import os
 import random
+import sys
 
 import pytest
 import torch
@@ -236,6 +237,25 @@ def test_rope_append_paged_exact(C, hd, page, t_max, fp8):
         C._rope_append_paged(qb, pos, tab, *pools, tbl, lens_t, t_max, page)
         assert torch.equal(_bits(qa), _bits(qb))
         _check_appended(pools, wholes, fills, caches, tbl, page, P, t_max)
+
+
+# ------------------------------------------- one local head of a tensor-parallel rank ----
+@pytest.fixture
+def one_head(monkeypatch):
+    """H = 1 for the helpers and test bodies of this module, which read it when they run."""
+    monkeypatch.setattr(sys.modules[__name__], "H", 1)
+
+
+@pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
+def test_attn_decode_paged_one_head(C, one_head, fp8):
+    """H = 1 at head_dim 64, T_max 300 in pages of 16: the cases of the test above, bit for bit."""
+    test_attn_decode_paged_is_bit_identical(C, 64, 300, 16, fp8)
+
+
+@pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
+def test_rope_append_paged_one_head(C, one_head, fp8):
+    """H = 1 at head_dim 64, pages of 16: the same rotated rows and cache bytes."""
+    test_rope_append_paged_exact(C, 64, 16, 40, fp8)
 
 
 # ------------------------------------------------------------------ 4. table safety ----

@@ -36,11 +36,11 @@ def _plumbing(rank, world):
     from distributed_pytorch_from_scratch_amd.models.engine_common import _Layer
     from distributed_pytorch_from_scratch_amd.ops import reference as R
     m, md, p = W8.tiny_model(), W8.tiny_model(), W8.prompt(3)
-    with torch.no_grad():                   # md: every projection weight replaced by its dequantised value
-        for L in map(_Layer, md.layers):
-            for w in (L.wqkv, L.wo, L.wgu, L.wd):
+    with torch.no_grad():                   # md: every coded projection weight replaced by its dequantised value
+        ws = [w for L in map(_Layer, md.layers) for w in (L.wqkv, L.wo, L.wgu, L.wd)] + [md.lm_head.weight]
+        for w in ws:                        # (a shard whose K is no multiple of 128, Wo at two ranks, has no codes)
+            if w.size(1) % 128 == 0:
                 w.copy_(R._dequant_w4(*R._quant_w4_rows(w)))
-        md.lm_head.weight.copy_(R._dequant_w4(*R._quant_w4_rows(md.lm_head.weight)))
     # the first decode step after the exact-weight prefill of m: m on its codes, md and m on their weights
     step = {}
     for name, mm, fmt in (("w4", m, "mxfp4"), ("deq", md, None), ("act", m, None)):
@@ -50,6 +50,7 @@ def _plumbing(rank, world):
         step[name] = G.logits_step(mm, torch.full((3, 1), 5), c)
     kw = dict(prompt_lens=[12, 7, 9], kv_dtype="fp8", temperature=[0.0, 0.8, 1.0], seed=3)
     out = {"routed": torch.equal(step["w4"], step["deq"]), "rel": N.rel(step["w4"], step["act"]),
+           "coded": len(G.quantise_weights(m, "cpu", "mxfp4")),
            # on md quantisation is the identity, prefill included: the same tokens with and without the codes
            "tokens": [G.generate(md, p, 6, weight_dtype=wd, **k) for wd in ("mxfp4", None) for k in ({}, kw)],
            "errs": {}}
@@ -67,11 +68,28 @@ def plumbing():
     return run_distributed(_plumbing, 1)[0]
 
 
+@pytest.fixture(scope="module")
+def plumbing_tp2():
+    return run_distributed(_plumbing, 2)
+
+
 def test_every_projection_runs_on_the_codes(plumbing):
+    assert plumbing["coded"] == 9
     t = plumbing["tokens"]
     assert plumbing["routed"] and t[0] == t[2] and t[1] == t[3] and [len(r) for r in t[1]] == [18, 13, 15]
     print("rel(MXFP4-weight logits, exact-weight logits), first decode step:", plumbing["rel"])   # reported, no threshold
     assert 0 < plumbing["rel"] < 1
+
+
+def test_two_ranks_agree(plumbing_tp2, plumbing):
+    """One local head per rank: Wo (K 64) keeps its bf16 weights, the other seven projections run on their
+    shard's codes, and both ranks return the same tokens."""
+    a, b = plumbing_tp2[0], plumbing_tp2[1]
+    assert a["coded"] == b["coded"] == 7 and a["routed"] and b["routed"]
+    assert a["tokens"] == b["tokens"] and a["rel"] == b["rel"] and 0 < a["rel"] < 1
+    t = a["tokens"]
+    assert t[0] == t[2] and t[1] == t[3] and [len(r) for r in t[1]] == [18, 13, 15]
+    assert a["errs"] == b["errs"] == plumbing["errs"]
 
 
 def test_refusals(plumbing):
