@@ -242,6 +242,61 @@ std::vector<torch::Tensor> quant_w4_rows(torch::Tensor w) {
   return {codes, scales};
 }
 
+// ------------------------------------------------- quantised weights, any M (prefill) --
+// The same codes on the large-M kernel (kernels/gemm_wq.hip): any M >= 1, no swiglu operand (the down
+// projection takes swiglu_fwd(x)).  Recorded in tests/golden/ext_api_wq.txt (tests/test_ext_api_wq.py).
+static bool wq_operands_ok(const torch::Tensor& x, const torch::Tensor& codes, int64_t K) {
+  if (!x.is_cuda() || !codes.is_cuda() || x.dim() != 2 || codes.dim() != 2 || x.scalar_type() != torch::kBFloat16 ||
+      codes.scalar_type() != torch::kUInt8 || x.stride(1) != 1 || codes.stride(1) != 1 || x.device() != codes.device())
+    return false;
+  if (x.size(1) != K || x.size(0) >= (1LL << 31) || codes.size(0) >= (1LL << 31) || K >= (1LL << 31)) return false;
+  return !(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 || reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16);
+}
+
+bool gemm_nt_w8_ok(torch::Tensor x, torch::Tensor codes) {
+  const int64_t K = codes.dim() == 2 ? codes.size(1) : 0;
+  return wq_operands_ok(x, codes, K) &&
+         dpfs_gemm_wq8_ok((int)x.size(0), (int)codes.size(0), (int)K, x.stride(0), codes.stride(0)) != 0;
+}
+
+// y[M, N] = bf16((x codes^T) * inv + bias) for any M >= 1: gemv_nt_w8's formula on the tiled kernel.
+torch::Tensor gemm_nt_w8(torch::Tensor x, torch::Tensor codes, torch::Tensor inv, c10::optional<torch::Tensor> bias) {
+  TORCH_CHECK(gemm_nt_w8_ok(x, codes),
+              "gemm_nt_w8: needs bf16 row-major x [M >= 1, K] (row stride % 8 == 0) and uint8 codes [N >= 1, K] "
+              "(row stride % 16 == 0) on one device, both 16-byte aligned, K % 64 == 0");
+  const int64_t M = x.size(0), N = codes.size(0), K = codes.size(1);
+  const at::DeviceGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  dpfs_gemm_wq8(x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), opt_f32(inv, N, "inv"),
+                opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M, (int)N, (int)K, stream());
+  return y;
+}
+
+bool gemm_nt_w4_ok(torch::Tensor x, torch::Tensor codes) {
+  const int64_t K = codes.dim() == 2 ? 2 * codes.size(1) : 0;
+  return wq_operands_ok(x, codes, K) &&
+         dpfs_gemm_wq4_ok((int)x.size(0), (int)codes.size(0), (int)K, x.stride(0), codes.stride(0), K / 32) != 0;
+}
+
+// y[M, N] = bf16(x wq^T + bias) for any M >= 1: gemv_nt_w4's formula on the tiled kernel.
+torch::Tensor gemm_nt_w4(torch::Tensor x, torch::Tensor codes, torch::Tensor scales,
+                         c10::optional<torch::Tensor> bias) {
+  TORCH_CHECK(gemm_nt_w4_ok(x, codes),
+              "gemm_nt_w4: needs bf16 row-major x [M >= 1, K] (row stride % 8 == 0) and uint8 codes [N >= 1, K / 2] "
+              "(row stride % 16 == 0) on one device, both 16-byte aligned, K % 128 == 0");
+  const int64_t M = x.size(0), N = codes.size(0), K = 2 * codes.size(1);
+  TORCH_CHECK(scales.is_cuda() && scales.device() == x.device() && scales.scalar_type() == torch::kUInt8 &&
+                  scales.dim() == 2 && scales.size(0) == N && scales.size(1) == K / 32 && scales.stride(1) == 1 &&
+                  scales.stride(0) % 4 == 0 && scales.stride(0) >= K / 32 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "gemm_nt_w4: scales must be a 4-byte aligned uint8 [N, K / 32] on x's device with a row stride % 4 == 0");
+  const at::DeviceGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  dpfs_gemm_wq4(x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0),
+                opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M, (int)N, (int)K, stream());
+  return y;
+}
+
 // rope_ on the q and k heads of the packed qkv rows + kv_append of the rotated k and v rows
 // at *len, one kernel (decode step).
 void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kc, torch::Tensor vc,
@@ -778,6 +833,10 @@ void bind_decode(py::module_& m) {
   m.def("_gemv_nt_w4", &gemv_nt_w4, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none(),
         py::arg("swiglu") = false);
   m.def("_quant_w4_rows", &quant_w4_rows, py::arg("w"));
+  m.def("_gemm_nt_w8_ok", &gemm_nt_w8_ok, py::arg("x"), py::arg("codes"));
+  m.def("_gemm_nt_w8", &gemm_nt_w8, py::arg("x"), py::arg("codes"), py::arg("inv"), py::arg("bias") = py::none());
+  m.def("_gemm_nt_w4_ok", &gemm_nt_w4_ok, py::arg("x"), py::arg("codes"));
+  m.def("_gemm_nt_w4", &gemm_nt_w4, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none());
   m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("len"));
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),

@@ -244,6 +244,16 @@ int dpfs_gemm_tn_group(int n, const void* const* A, const void* const* B, float*
                        const void* const* A2, const void* const* B2, const int* lda2, const int* ldb2, int K1,
                        hipStream_t s);
 
+// kernels/gemm_wq.hip
+// quantised-weight GEMM for any M (the prefill and batches above 64) on the codes of the two formats
+// below: wq8 = e4m3 codes + fp32 inv (gemv_w8.hip), wq4 = e2m1 codes + e8m0 scales (gemv_w4.hip)
+int dpfs_gemm_wq8_ok(int M, int N, int K, long long lda, long long ldc);
+void dpfs_gemm_wq8(const void* A, long long lda, const void* codes, long long ldc, const float* inv,
+                   const float* bias, void* Y, long long ldy, int M, int N, int K, hipStream_t s);
+int dpfs_gemm_wq4_ok(int M, int N, int K, long long lda, long long ldc, long long lds);
+void dpfs_gemm_wq4(const void* A, long long lda, const void* codes, long long ldc, const void* scales,
+                   long long lds, const float* bias, void* Y, long long ldy, int M, int N, int K, hipStream_t s);
+
 // kernels/gemv_w4.hip
 // weight-only MXFP4 decode projections: e2m1 codes [N, K / 2] (row stride ldc bytes, low nibble
 // first) with e8m0 scales [N, K / 32] (row stride lds bytes), K % 128 == 0

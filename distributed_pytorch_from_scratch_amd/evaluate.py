@@ -96,7 +96,10 @@ def get_test_args(argv=None):
     g.add_argument("--weight_dtype", choices=["act", "fp8", "mxfp4"], default="act",
                    help="projection weights of the one-token decode steps: the activation dtype, e4m3 codes "
                         "with one fp32 scale per output channel, or OCP MXFP4 (e2m1 codes, one e8m0 scale per "
-                        "32 k) (KV-cached decoding; the prefill keeps bf16)")
+                        "32 k) (KV-cached decoding; the prefill keeps bf16 unless --quantised_prefill)")
+    g.add_argument("--quantised_prefill", action="store_true",
+                   help="with --weight_dtype fp8 / mxfp4: the prefill and every extend piece on the weight codes "
+                        "too (one model for the prompt and the generated tokens), and no batch cap of 64")
     g.add_argument("--kv_page", type=int, default=0,
                    help="keep the KV cache in pages of this many tokens (a power of two in [16, 256]; 0: contiguous)")
     g.add_argument("--kv_pool_pages", type=int, default=0,
@@ -127,7 +130,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                   prefill_chunk: int = 0, kv_dtype=None, repetition_penalty=1.0, presence_penalty=0.0,
                   frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None,
-                  weight_dtype=None):
+                  weight_dtype=None, quantised_prefill: bool = False):
     """Greedy continuation of ``[bos] + prompt`` until EOS or ``max_len + 1`` tokens (the
     reference's stopping rule, ``test.py:144-150``); returns the ids after BOS without EOS.
     ``kv_cache`` decodes one token per step against cached keys/values
@@ -139,7 +142,8 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
     KV cache as e4m3 codes (``generate``).  The three penalties are ``generate``'s (KV-cached
     decoding only); ``return_logprobs`` returns (ids, the model's log-probability of every
     generated id, a final EOS included) instead of the ids.  ``kv_page`` / ``kv_pool_pages`` page
-    the KV cache (``generate``; KV-cached decoding only)."""
+    the KV cache (``generate``; KV-cached decoding only); ``weight_dtype`` / ``quantised_prefill`` are
+    ``generate``'s."""
     pen = (repetition_penalty, presence_penalty, frequency_penalty) != (1.0, 0.0, 0.0) or return_logprobs
     if not kv_cache and (temperature != 0 or isinstance(seed, (list, tuple, torch.Tensor)) or pen):
         raise ValueError("sampling (--temperature > 0), penalties and log-probabilities run in the KV-cached decode "
@@ -152,7 +156,7 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
                        top_k=top_k, top_p=top_p, seed=seed, prefill_chunk=prefill_chunk, kv_dtype=kv_dtype,
                        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                        frequency_penalty=frequency_penalty, return_logprobs=return_logprobs, kv_page=kv_page,
-                       kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype)
+                       kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype, quantised_prefill=quantised_prefill)
         out, lps = (out[0][0], out[1][0]) if return_logprobs else (out[0], None)
         out = out[1:]
         if out and out[-1] == eos and len(out) > len(prompt_ids):
@@ -175,7 +179,8 @@ def greedy_decode(model: Transformer, prompt_ids, bos: int, eos: int, max_len: i
 def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len: int, dev, temperature: float = 0.0,
                         top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None,
                         repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None, weight_dtype=None):
+                        return_logprobs: bool = False, kv_page: int = 0, kv_pool_pages=None, weight_dtype=None,
+                        quantised_prefill: bool = False):
     """``greedy_decode`` of several prompts (lists of ids of any lengths) as one ragged KV-cached
     batch: per prompt, the ids after BOS without a trailing EOS, each row stopped by the
     reference's rule (EOS, or ``max_len + 1`` tokens in all).  With sampling, row b draws with
@@ -194,7 +199,7 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
         return [greedy_decode(model, p, bos, eos, max_len, dev, True, row(temperature, b), row(top_k, b),
                               row(top_p, b), row(seed, b), prefill_chunk, kv_dtype, repetition_penalty,
                               presence_penalty, frequency_penalty, return_logprobs, kv_page, kv_pool_pages,
-                              weight_dtype)
+                              weight_dtype, quantised_prefill)
                 for b, p in enumerate(prompts)]
     tokens = torch.zeros(len(prompts), max(lens), dtype=torch.long, device=dev)
     for b, p in enumerate(prompts):
@@ -204,7 +209,7 @@ def greedy_decode_batch(model: Transformer, prompts, bos: int, eos: int, max_len
                     prefill_chunk=prefill_chunk, kv_dtype=kv_dtype, repetition_penalty=repetition_penalty,
                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                     return_logprobs=return_logprobs, kv_page=kv_page, kv_pool_pages=kv_pool_pages,
-                    weight_dtype=weight_dtype)
+                    weight_dtype=weight_dtype, quantised_prefill=quantised_prefill)
     outs, lps = outs if return_logprobs else (outs, [None] * len(prompts))
     res = []
     for p, out, lp in zip(prompts, outs, lps):
@@ -275,6 +280,8 @@ def test(rank, args):
         sampling["kv_dtype"] = args.kv_cache_dtype
     if args.weight_dtype != "act":
         sampling["weight_dtype"] = args.weight_dtype
+    if args.quantised_prefill:
+        sampling["quantised_prefill"] = True
     pens = dict(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                 frequency_penalty=args.frequency_penalty)
     if pens != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
@@ -346,6 +353,8 @@ def main(argv=None):
         raise ValueError("--kv_cache_dtype chooses the storage of the KV cache: drop --no_kv_cache")
     if args.weight_dtype != "act" and args.no_kv_cache:
         raise ValueError("--weight_dtype chooses the weights of the KV-cached decode steps: drop --no_kv_cache")
+    if args.quantised_prefill and args.weight_dtype == "act":
+        raise ValueError("--quantised_prefill runs the prefill on the weight codes: give --weight_dtype fp8 or mxfp4")
     check_kv_page_args(args)
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)

@@ -67,6 +67,14 @@ MXFP4 weights (``weight_dtype="mxfp4"``): the same projections on OCP MX codes, 
 e8m0 scale per 32 consecutive k (``_quant_w4_rows``; ``_gemv_nt_w4``, csrc/kernels/gemv_w4.hip: 0.53
 bytes per parameter), under the rules of the fp8 weights and kept as ``cache.w4``.
 
+Quantised prefill (``quantised_prefill=True`` with a ``weight_dtype``; recorded as ``cache.wq_prefill``
+and in the session key): every projection of the session runs on its codes, so the prompt and the
+generated tokens go through one model.  A prefill or extend piece then takes ``_layers_on_codes``, the
+kernels and order of ``decode_step`` on B*T rows with the attention part of the module path
+(``_attend``); projections of more than 64 rows, decode batches above 64 included, run on the tiled
+MFMA GEMM on codes (``_gemm_nt_w8`` / ``_gemm_nt_w4``, csrc/kernels/gemm_wq.hip), those of up to 64 rows
+on the decode kernels (``_projector``).
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -101,6 +109,7 @@ class KVCache:
     page = 0    # the page size of a ``PagedKVCache``; 0: this contiguous form
     w8 = None   # fp8 decode weights of the session (``quantise_weights``); None: bf16 weights
     w4 = None   # MXFP4 decode weights of the session (``quantise_weights``); None: bf16 or fp8 weights
+    wq_prefill = False   # ``quantised_prefill``: every projection of the session on its codes, at any row count
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
                  ragged: bool = False, kv_dtype: Optional[str] = None):
@@ -355,13 +364,16 @@ W8_MAX_BATCH = 64     # rows of the quantised-weight projection kernels (gemv_w8
 WEIGHT_DTYPES = {"fp8": 64, "mxfp4": 128}     # weight_dtype -> the K multiple its kernel takes
 
 
-def _check_weight_dtype(model, B: int, weight_dtype, who: str = "generate") -> None:
+def _check_weight_dtype(model, B: int, weight_dtype, who: str = "generate", quantised_prefill: bool = False) -> None:
     if weight_dtype is None:
+        if quantised_prefill:
+            raise ValueError(f"{who}: quantised_prefill=True needs a weight_dtype ('fp8' or 'mxfp4'): it runs the "
+                             "prefill on the session's weight codes")
         return
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"{who}: weight_dtype must be None (the activation dtype), 'fp8' or 'mxfp4', got "
                          f"{weight_dtype!r}")
-    if B > W8_MAX_BATCH:
+    if B > W8_MAX_BATCH and not quantised_prefill:     # (with it, more rows take gemm_wq_k)
         raise ValueError(f"{who}: weight_dtype={weight_dtype!r} decodes at most {W8_MAX_BATCH} sequences per batch, "
                          f"got {B}")
     if model.args.norm != "rmsnorm":
@@ -470,8 +482,53 @@ def _draw(logits: torch.Tensor, vocab: int, sample, pos: torch.Tensor) -> torch.
     return K(logits).sample_logits(logits, vocab, *sample, pos)[0]
 
 
+def _projector(cache: KVCache, k, dt, rows: int):
+    """``proj(a, w, bias=None, swiglu=False)`` of a step or prefill piece of ``rows`` rows: y = a w^T
+    (+ bias), a = silu(gate) * up of the packed ``a`` with ``swiglu``.
+
+    fp8 weights (cache.w8): the session's codes of this parameter, on gemv_w8_k up to 64 rows and, in a
+    ``quantised_prefill`` session (``cache.wq_prefill``), on gemm_wq_k above (after a ``swiglu_fwd`` pass,
+    whose rounding is the fused operand's).  A projection without codes (K % 64 != 0) or whose operands
+    the kernel declines (a pinned library backend) keeps the bf16 route; with d, the local head width
+    and the local ffn width all multiples of 64 no projection falls back.  MXFP4 weights (cache.w4): the
+    same on gemv_w4_k / gemm_wq_k, with 128 for 64."""
+    small = rows <= 16
+    big = cache.wq_prefill and rows > W8_MAX_BATCH
+    if cache.w4 is not None:
+        wq, small_q, big_q = cache.w4, GS.small_nt_w4, GS.big_nt_w4
+    else:
+        wq, small_q, big_q = cache.w8 or {}, GS.small_nt_w8, GS.big_nt_w8
+
+    def proj(a, w, bias=None, swiglu=False):
+        q = wq.get(id(w))
+        if q is not None and big:
+            a, swiglu = (k.swiglu_fwd(a) if swiglu else a), False
+            y = big_q(k, a, q, bias)
+        elif q is not None:
+            y = small_q(k, a, q, bias, swiglu)
+        else:
+            y = None
+        if y is not None:
+            return y
+        w = shadow(w, dt)
+        if small:   # MFMA GEMV-class kernel, SwiGLU fused into the down projection's operand
+            return GS.small_nt(k, a, w, bias, swiglu)
+        return GS.gemm_nt(k, k.swiglu_fwd(a) if swiglu else a, w, bias)
+    return proj
+
+
 def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int, T: int, n_t=None):
-    """Multi-token step (prefill, or T > 1 continuation) with host-side cache bookkeeping.  The
+    """Multi-token step (prefill, or T > 1 continuation) through the module's projections: QKV,
+    ``_attend``, Wo."""
+    attn = layer.attn
+    h, hd = attn.num_local_heads, attn.head_dim
+    qkv = attn.wqkv(x2d)                                     # (B*T, 3*h*hd)
+    return attn.wo(_attend(qkv, h, hd, positions, tab, cache, li, B, T, n_t))
+
+
+def _attend(qkv, h: int, hd: int, positions, tab, cache: KVCache, li: int, B: int, T: int, n_t=None):
+    """RoPE, cache append and attention of a multi-token step (prefill, or T > 1 continuation) on the
+    packed ``qkv`` rows (B*T, 3*h*hd), with host-side cache bookkeeping; returns o (B*T, h*hd).  The
     continuation (``cache.len > 0``) reads the cache lengths from ``cache.len_t`` (the caller has
     run ``cache.sync_device_len()``); ``n_t`` (device int32 (B,), or None for T) gives the real
     new tokens of every right-padded row.
@@ -481,9 +538,6 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
     length 0 (``cache.len_t`` holds 0 there: the caller has synchronised it), the rows the slice
     copy writes.  A continuation appends and attends through the ``_q8`` kernels, so its queries
     see the quantised prefix and the quantised rows of their own chunk."""
-    attn = layer.attn
-    h, hd = attn.num_local_heads, attn.head_dim
-    qkv = attn.wqkv(x2d)                                     # (B*T, 3*h*hd)
     k_ = K(qkv)
     k_.rope_(qkv, positions, tab, 2 * h, hd, False)
     scale = 1.0 / math.sqrt(hd)
@@ -519,7 +573,33 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
         # then its T new queries attend the cached prefix plus the causal part of the chunk
         k_._kv_append_chunk(qkv, cache.k[li], cache.v[li], cache.len_t, n_t)
         o = k_._attn_extend(qkv, cache.k[li], cache.v[li], cache.len_t, n_t, scale)
-    return attn.wo(o.reshape(B * T, h * hd))
+    return o.reshape(B * T, h * hd)
+
+
+def _layers_on_codes(model, x, positions, tab, cache: KVCache, B: int, T: int, n_t):
+    """The layers of a prefill piece in a ``quantised_prefill`` session (RMSNorm model, bf16 compute on
+    the GPU): the kernels and the order of ``decode_step`` on B*T rows, every projection on the session's
+    codes (``_projector``), the attention part that of the module path (``_attend``).  ``x`` (B*T, D);
+    returns the hidden states in front of the final norm."""
+    from .engine_common import _Layer
+    k = K(model.embedding.weight, x.dtype)
+    proj = _projector(cache, k, x.dtype, B * T)
+    pend = pend_bias = None
+    for li, layer in enumerate(model.layers):
+        L = _Layer(layer)
+        if pend is None:
+            h1, _ = k.rmsnorm_fwd(x, L.s1, L.eps1)
+        else:
+            x, h1, _ = k.add_rmsnorm_fwd(pend, pend_bias, x, L.s1, L.eps1)
+        o = _attend(proj(h1, L.wqkv, L.bqkv), L.h, L.hd, positions, tab, cache, li, B, T, n_t)
+        pout = proj(o, L.wo)
+        tp_comm.all_reduce(pout, async_op=False)
+        x, h2, _ = k.add_rmsnorm_fwd(pout, L.bo, x, L.s2, L.eps2)
+        pend, pend_bias = proj(proj(h2, L.wgu, L.bgu), L.wd, swiglu=True), L.bd
+        tp_comm.all_reduce(pend, async_op=False)
+    # (the last down projection's bias + residual; the norm's own output is not used: the caller
+    # norms the rows it keeps)
+    return k.add_rmsnorm_fwd(pend, pend_bias, x, model.norm.scale, model.norm.eps)[0]
 
 
 def _prefill_piece(model, ids: torch.Tensor, cache: KVCache, n: Optional[List[int]]) -> torch.Tensor:
@@ -549,9 +629,12 @@ def _prefill_piece(model, ids: torch.Tensor, cache: KVCache, n: Optional[List[in
         if n is not None:
             n_t = torch.tensor(n, dtype=torch.int32, device=dev)
     tab = model.rope_table(dev)
-    for li, layer in enumerate(model.layers):
-        x = x + _attention_step(layer, layer.norm1(x), positions, tab, cache, li, B, T, n_t)
-        x = x + layer.ffn(layer.norm2(x))
+    if cache.wq_prefill:
+        x = _layers_on_codes(model, x, positions, tab, cache, B, T, n_t)
+    else:
+        for li, layer in enumerate(model.layers):
+            x = x + _attention_step(layer, layer.norm1(x), positions, tab, cache, li, B, T, n_t)
+            x = x + layer.ffn(layer.norm2(x))
     if cache.ragged:
         cache.set_lens(c + m for c, m in zip(cache.lens, n if n is not None else [T] * B))
     else:
@@ -618,7 +701,11 @@ def logits_step(model, ids: torch.Tensor, cache: KVCache, lens=None, prefill_chu
             h = x.new_empty(B, x.size(-1)) if h is None else h
             h[rows] = x[rows, [last[b] - s for b in rows]]
     h = model.norm(h)
-    logits = model._lm_head_local(h)
+    if cache.wq_prefill:    # the lm_head of the last rows on its codes too, as in decode_step
+        logits = _projector(cache, K(model.embedding.weight, h.dtype), h.dtype, B)(
+            h, model.lm_head.weight, model.lm_head.bias)
+    else:
+        logits = model._lm_head_local(h)
     logits = comm_ops.Gather.apply(logits, model.lm_head.sizes)
     return logits[..., : model.vocab_size].float()
 
@@ -654,29 +741,11 @@ def decode_step(model, ids: torch.Tensor, pos: torch.Tensor, cache: KVCache, sam
     dev = ids.device
     dt = model.act_dtype(dev)
     k = K(model.embedding.weight, dt)
-    W = lambda w: shadow(w, dt) if w is not None else None
     model.embedding.out_dtype = dt
     x = model.embedding(ids).reshape(B, -1).to(dt)
     tab = model.rope_table(dev)
     pend = pend_bias = None
-    small = B <= 16
-    wq, small_q = (cache.w4, GS.small_nt_w4) if cache.w4 is not None else (cache.w8 or {}, GS.small_nt_w8)
-
-    def proj(a, w, bias=None, swiglu=False):
-        # fp8 weights (cache.w8, B <= 64): gemv_w8_k on the session's codes of this parameter.  A
-        # projection without codes (K % 64 != 0) or whose operands the kernel declines (a pinned
-        # library backend) keeps the bf16 route below; with d, the local head width and the local
-        # ffn width all multiples of 64 no projection falls back.  MXFP4 weights (cache.w4): the
-        # same on gemv_w4_k, with 128 for 64.
-        q = wq.get(id(w))
-        if q is not None:
-            y = small_q(k, a, q, bias, swiglu)
-            if y is not None:
-                return y
-        w = W(w)
-        if small:   # MFMA GEMV-class kernel, SwiGLU fused into the down projection's operand
-            return GS.small_nt(k, a, w, bias, swiglu)
-        return GS.gemm_nt(k, k.swiglu_fwd(a) if swiglu else a, w, bias)
+    proj = _projector(cache, k, dt, B)     # bf16 weights, or the session's fp8 / MXFP4 codes
     # Per layer: [bias + residual +] RMSNorm (one kernel), QKV projection, RoPE + append of
     # k/v at len (one kernel), split-K decode attention, Wo projection, bias + residual +
     # RMSNorm, gate|up projection, SwiGLU + down projection (its bias + residual fold into the
@@ -842,7 +911,8 @@ _SESSIONS = {}   # (id(model), B, t_max, device, kv_dtype, ragged[, kv_page, kv_
 
 
 def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Optional[str] = None,
-             kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
+             kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None,
+             quantised_prefill: bool = False):
     """The KV cache and decode graphs for this (model, batch, length, cache dtype, uniform /
     ragged, page size, pool pages): reused
     by the next generate() call of the same shape, so serving pays the graph capture once (a
@@ -858,13 +928,15 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     ends in ("weights", "fp8"),
     behind everything the shape comparison below indexes; the codes (``quantise_weights``) hang on
     the session's cache as ``cache.w8``, its graphs replay them, and like the graphs they are
-    rebuilt with the session when any parameter's version moves."""
+    rebuilt with the session when any parameter's version moves.  ``quantised_prefill`` (the prefill and
+    batches above 64 on the codes too, ``cache.wq_prefill``) is part of that key element: such a
+    session is apart from the plain ``weight_dtype`` one, whose graphs and results stay what they were."""
     attn0 = model.layers[0].attn
     key = (id(model), B, t_max, str(dev), kv_dtype, ragged)
     if kv_page:
         key += (kv_page, kv_pool_pages)
     if weight_dtype:
-        key += (("weights", weight_dtype),)
+        key += (("weights", weight_dtype) + (("prefill",) if quantised_prefill else ()),)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
@@ -880,6 +952,7 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
         cache.w8 = quantise_weights(model, dev)
     elif weight_dtype == "mxfp4":
         cache.w4 = quantise_weights(model, dev, "mxfp4")
+    cache.wq_prefill = bool(weight_dtype and quantised_prefill)
     graphs = {}
     kv_bytes = cache.nbytes()             # the fp8 form: codes and scales; the paged form: pools and table
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
@@ -916,7 +989,8 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
              seed=0, prompt_lens=None, prefill_chunk: int = 0,
              kv_dtype: Optional[str] = None, repetition_penalty=1.0, presence_penalty=0.0,
              frequency_penalty=0.0, return_logprobs: bool = False, kv_page: int = 0,
-             kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
+             kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None,
+             quantised_prefill: bool = False):
     """Decoding with a KV cache. ``prompt`` (B, T0) int64. Returns, per sequence, the
     prompt plus the generated ids. A sequence stops after emitting ``eos_id`` (kept in the
     output) or when the total length reaches ``max_len`` (default: model maxlen).
@@ -996,8 +1070,18 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     elements with one e8m0 scale per 32 consecutive k (``_quant_w4_rows``, round to nearest;
     ``_gemv_nt_w4``, csrc/kernels/gemv_w4.hip: a quarter of the bf16 weight bytes plus the scales),
     under the same rules with 128 for 64; its row-parallel partial sums need no scale.  ``None``,
-    the default, is every path above unchanged."""
-    _check_weight_dtype(model, prompt.size(0), weight_dtype)
+    the default, is every path above unchanged.
+
+    ``quantised_prefill=True`` (needs a ``weight_dtype``; ``ValueError`` without) runs EVERY projection of
+    the session on its codes, so the prompt and the generated tokens see one model: the prefill, whole
+    or chunked, and every extend piece go through the kernels of the decode step on B*T rows, their
+    projections on ``_gemm_nt_w8`` / ``_gemm_nt_w4`` (csrc/kernels/gemm_wq.hip: the tiled MFMA GEMM on
+    codes, each converted once per workgroup) above 64 rows and on the decode kernels up to 64; the
+    last rows' lm_head likewise; and the batch cap of 64 is lifted, decode steps of more rows take the
+    tiled kernel.  A weight without codes keeps its bf16 route as above.  The bf16 weights stay loaded
+    (the embedding, the norms and the biases are read from the model as ever).  ``False``, the default,
+    changes nothing."""
+    _check_weight_dtype(model, prompt.size(0), weight_dtype, quantised_prefill=quantised_prefill)
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")
     if prefill_chunk < 0:
@@ -1029,9 +1113,10 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
         lens = _check_lens(prompt_lens, B, T0) if prompt_lens is not None else [T0] * B
         return _generate_ragged(model, prompt, lens, max_new_tokens, eos_id, max_len,
                                 sample, prefill_chunk, kv_dtype, return_logprobs, kv_page, kv_pool_pages,
-                                weight_dtype)
+                                weight_dtype, quantised_prefill)
     t_max = min(model.args.maxlen, max_len or model.args.maxlen, T0 + max_new_tokens)
-    cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype, weight_dtype=weight_dtype)
+    cache, graphs = _session(model, B, t_max, dev, kv_dtype=kv_dtype, weight_dtype=weight_dtype,
+                             quantised_prefill=quantised_prefill)
     out = [list(map(int, row)) for row in prompt.tolist()]
     lps = [[] for _ in range(B)]          # (logp_model, logp_sampled) per generated id (the "pen" form)
     result = lambda: (out, lps) if return_logprobs else out
@@ -1096,7 +1181,8 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
 
 def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_tokens: int, eos_id, max_len, sample,
                      prefill_chunk: int = 0, kv_dtype: Optional[str] = None, return_logprobs: bool = False,
-                     kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None):
+                     kv_page: int = 0, kv_pool_pages: Optional[int] = None, weight_dtype: Optional[str] = None,
+                     quantised_prefill: bool = False):
     """generate() for per-row prompt lengths ``lens`` (see there).  Every row is fed to every
     step, finished or not; the host drops the ids of a finished row, and the device keeps a row
     that has filled the cache frozen inside it (``_step_advance_rows``).  With ``kv_page`` the
@@ -1107,7 +1193,8 @@ def _generate_ragged(model, prompt: torch.Tensor, lens: List[int], max_new_token
     cap = min(model.args.maxlen, max_len or model.args.maxlen)     # total length at which a row stops
     t_max = min(cap, max(lens) + max_new_tokens)
     cache, graphs = _session(model, B, t_max, dev, ragged=True, kv_dtype=kv_dtype, kv_page=kv_page,
-                             kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype)
+                             kv_pool_pages=kv_pool_pages, weight_dtype=weight_dtype,
+                             quantised_prefill=quantised_prefill)
     rows = prompt.tolist()
     out = [list(map(int, rows[b][:lens[b]])) for b in range(B)]
     lps = [[] for _ in range(B)]

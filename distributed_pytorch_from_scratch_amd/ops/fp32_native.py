@@ -98,6 +98,14 @@ def _gemv_nt_w4_ok(x, codes, swiglu: bool = False) -> bool:
     return False     # MXFP4 weights likewise
 
 
+def _gemm_nt_w8_ok(x, codes) -> bool:
+    return False     # the large-M forms of the two
+
+
+def _gemm_nt_w4_ok(x, codes) -> bool:
+    return False
+
+
 # single-token decode (models/generation.py): bf16 kernels only; fp32 decode on tensor ops
 # (the token choice, sample_logits / _sample_logits_rows / _sample_logits_pen, takes fp32 rows
 # too and reaches the kernel through __getattr__ below)

@@ -340,6 +340,30 @@ def small_nt_w4(k, x: torch.Tensor, w4, bias=None, swiglu: bool = False) -> Opti
     return None
 
 
+def big_nt_w8(k, x: torch.Tensor, w8, bias=None) -> Optional[torch.Tensor]:
+    """``gemm_nt`` on fp8 weights, any number of rows (the callers route M > 64 here: prefill and extend
+    pieces, batches above 64): ``w8`` as in ``small_nt_w8``; y = (x codes^T) * inv (+ bias) on gemm_wq_k
+    (csrc/kernels/gemm_wq.hip: every code converted once per workgroup into LDS).  None where the kernel
+    does not take the shape (K % 64, strides) or the library backend is pinned: the caller keeps its bf16
+    route for that projection."""
+    codes, inv = w8
+    if _direct(k) or not x.is_cuda:
+        return k._gemm_nt_w8(x, codes, inv, bias)
+    if mode() != "blas" and k._gemm_nt_w8_ok(x, codes):
+        return k._gemm_nt_w8(x, codes, inv, bias)
+    return None
+
+
+def big_nt_w4(k, x: torch.Tensor, w4, bias=None) -> Optional[torch.Tensor]:
+    """``big_nt_w8`` on MXFP4 weights: ``w4`` as in ``small_nt_w4``; y = x wq^T (+ bias), K % 128."""
+    codes, scales = w4
+    if _direct(k) or not x.is_cuda:
+        return k._gemm_nt_w4(x, codes, scales, bias)
+    if mode() != "blas" and k._gemm_nt_w4_ok(x, codes):
+        return k._gemm_nt_w4(x, codes, scales, bias)
+    return None
+
+
 def gemm_nn(k, a: torch.Tensor, b: torch.Tensor, out=None) -> torch.Tensor:
     """c[M,N] = a[M,K] b[K,N] in a.dtype (into ``out`` when given)."""
     fw = F8.lookup(b, dgrad=True)

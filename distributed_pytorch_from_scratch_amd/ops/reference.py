@@ -527,6 +527,27 @@ def _gemv_nt_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, bias
     return gemv_nt(x, _dequant_w4(codes, scales), bias, swiglu)
 
 
+def _gemm_nt_w8_ok(x: torch.Tensor, codes: torch.Tensor) -> bool:
+    return True
+
+
+def _gemm_nt_w8(x: torch.Tensor, codes: torch.Tensor, inv: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``_gemv_nt_w8`` for any number of rows (the GPU's tiled kernel, csrc/kernels/gemm_wq.hip): the same
+    formula, no ``swiglu`` operand."""
+    return _gemv_nt_w8(x, codes, inv, bias)
+
+
+def _gemm_nt_w4_ok(x: torch.Tensor, codes: torch.Tensor) -> bool:
+    return True
+
+
+def _gemm_nt_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``_gemv_nt_w4`` for any number of rows, no ``swiglu`` operand."""
+    return _gemv_nt_w4(x, codes, scales, bias)
+
+
 def rope_append(qkv: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, len: torch.Tensor) -> None:
     """rope_ on the q and k heads of the packed rows, then kv_append (one GPU kernel)."""

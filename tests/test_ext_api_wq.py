@@ -1,0 +1,35 @@
+"""The quantised-weight GEMM bindings of ``_C`` against ``tests/golden/ext_api_wq.txt`` (the pattern of
+``tests/test_ext_api_w8.py``); ``python tests/test_ext_api_wq.py`` re-records an intended change."""
+import glob
+import importlib
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ext_api_wq.txt")
+NAMES = ["_gemm_nt_w8", "_gemm_nt_w8_ok", "_gemm_nt_w4", "_gemm_nt_w4_ok"]
+
+
+def dump(mod) -> str:
+    return "".join(f"== {n}\n{(getattr(mod, n).__doc__ or '').strip()}\n" for n in NAMES)
+
+
+@pytest.mark.skipif(not glob.glob(os.path.join(ROOT, "distributed_pytorch_from_scratch_amd", "_C.*.so")),
+                    reason="the native extension is not built")
+def test_wq_bindings_match_golden():
+    import torch  # noqa: F401  (the extension links against it)
+    mod = importlib.import_module("distributed_pytorch_from_scratch_amd._C")
+    for n in NAMES:
+        assert hasattr(mod, n) and not hasattr(mod, n[1:])        # one binding each, under this name
+    with open(GOLDEN) as f:
+        assert dump(mod) == f.read()
+
+
+if __name__ == "__main__":
+    import sys
+    sys.path.insert(0, ROOT)
+    import torch  # noqa: F401
+    with open(GOLDEN, "w") as f:
+        f.write(dump(importlib.import_module("distributed_pytorch_from_scratch_amd._C")))
+    print("wrote", GOLDEN)

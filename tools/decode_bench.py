@@ -61,6 +61,12 @@ and MXFP4 in the same rounds.  ``--layers N`` builds the preset with N layers (a
 ``--w8-kernel`` times the projection launch alone on the preset's QKV, Wo, gate|up, down and
 lm_head shapes: ``_gemv_nt_w8`` and ``_gemv_nt_w4`` against ``gemv_nt`` (M <= 16) or the ``gemm_nt``
 route (M > 16), 100 launches per graph replay, with weight bytes / time (``w8_kernel_bench``).
+
+``--quantised-prefill`` adds to ``--prefill-chunk`` and ``--continuation`` the sessions on fp8 and MXFP4
+codes, with ``quantised_prefill`` off (the prefill on bf16 weights) and on (every projection on codes), in
+the same interleaved rounds.  ``--wq-kernel`` times the quantised-weight GEMM launch alone
+(``_gemm_nt_w8`` / ``_gemm_nt_w4``, csrc/kernels/gemm_wq.hip) against ``gemm_nt`` on the bf16 weight, on the
+preset's projection shapes at every ``--batch`` M (``wq_kernel_bench``).
 """
 from __future__ import annotations
 
@@ -109,6 +115,10 @@ def main():
     ap.add_argument("--layers", type=int, default=0, help="build the preset with this many layers (0: its own)")
     ap.add_argument("--w8-kernel", action="store_true",
                     help="time the fp8- and MXFP4-weight projection launches alone")
+    ap.add_argument("--quantised-prefill", action="store_true",
+                    help="--prefill-chunk / --continuation: also on fp8 and MXFP4 codes, quantised_prefill off and on")
+    ap.add_argument("--wq-kernel", action="store_true",
+                    help="time the quantised-weight GEMM launches (gemm_wq.hip) against gemm_nt at every --batch M")
     a = ap.parse_args()
     if a.kv_page and not a.ragged:
         ap.error("--kv-page runs the ragged decode benchmark: give --ragged")
@@ -142,6 +152,8 @@ def main():
     args = get_preset(a.model, **({"num_layers": a.layers} if a.layers else {}))
     if a.w8_kernel:
         return w8_kernel_bench(a, args)
+    if a.wq_kernel:
+        return wq_kernel_bench(a, args)
     if a.continuation and a.t0 + a.chunk > args.maxlen:     # the RoPE table must cover the continuation
         args = get_preset(a.model, maxlen=a.t0 + a.chunk)
     m = Transformer.from_args(args).cuda()
@@ -438,21 +450,73 @@ def w8_kernel_bench(a, args):
                                   "share_of_peak": round(floor / med, 3)}), flush=True)
 
 
+def wq_kernel_bench(a, args):
+    """``--wq-kernel``: us per launch of ``_gemm_nt_w8`` / ``_gemm_nt_w4`` and of ``gemm_nt`` on the bf16
+    weight, on the preset's projection shapes at every ``--batch`` M, 20 launches per timed window, in
+    interleaved rounds; one JSON line per (projection, M, kernel)."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.ops import _ext
+    C = _ext.require()
+    d, f, v = args.attn_dim, args.ffn_dim, (args.vocab_size + 127) // 128 * 128
+    for name, N, K in (("qkv", 3 * d, d), ("wo", d, d), ("gate_up", 2 * f, d), ("down", d, f), ("lm_head", v, d)):
+        w = (torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16()
+        q8, q4 = C._quant_w8_rows(w), C._quant_w4_rows(w) if K % 128 == 0 else None
+        for M in a.batch:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            launch = {"gemm_nt": lambda: C.gemm_nt(x, w), "w8": lambda: C._gemm_nt_w8(x, *q8)}
+            if q4:
+                launch["w4"] = lambda: C._gemm_nt_w4(x, *q4)
+            us = {k_: [] for k_ in launch}
+            for fn in launch.values():
+                fn()
+            for _ in range(max(a.repeats, 5)):
+                for k_, fn in launch.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[k_].append(round(50 * e0.elapsed_time(e1), 2))
+            for k_ in launch:
+                med = _median(us[k_])
+                print(json.dumps({"bench": "wq_kernel", "model": a.model, "proj": name, "M": M, "N": N, "K": K,
+                                  "kernel": k_, "us_per_call": us[k_], "us_per_call_median": med,
+                                  "tflops": round(2e-6 * M * N * K / med, 1),
+                                  "vs_gemm_nt": round(med / _median(us["gemm_nt"]), 3)}), flush=True)
+
+
+def _weight_forms(a, m):
+    """(label, cache attributes) of the sessions a prefill / continuation case times: bf16 weights, and with
+    ``--quantised-prefill`` the fp8 and MXFP4 codes with the option off (prefill on bf16 weights) and on."""
+    from distributed_pytorch_from_scratch_amd.models.generation import quantise_weights
+    forms = [("act", {})]
+    if a.quantised_prefill:
+        for wd, attr in (("fp8", "w8"), ("mxfp4", "w4")):
+            codes = quantise_weights(m, "cuda", wd)
+            forms += [(f"{wd} off", {attr: codes}), (f"{wd} on", {attr: codes, "wq_prefill": True})]
+    return forms
+
+
 def prefill_bench(a, m):
     """Time to first token (ms) and peak bytes above the cache of the prefill of ``--prompt`` ids,
-    whole (chunk 0) and in pieces, in interleaved rounds; one JSON line per (batch, chunk)."""
+    whole (chunk 0) and in pieces, in interleaved rounds; one JSON line per (batch, chunk, weight form)."""
     import torch
     from distributed_pytorch_from_scratch_amd.models.generation import logits_step
-    chunks = [0] + [c for c in a.prefill_chunk if c > 0]
+    forms = _weight_forms(a, m)
+    chunks = [(c, f) for c in [0] + [c for c in a.prefill_chunk if c > 0] for f in range(len(forms))]
     for B in a.batch:
         prompt = torch.randint(0, m.args.vocab_size, (B, a.prompt), device="cuda")
-        cache = _new_cache(m, B, a.prompt)
+        caches = [_new_cache(m, B, a.prompt) for _ in forms]
+        for cache, (_, attrs) in zip(caches, forms):
+            for k_, v_ in attrs.items():
+                setattr(cache, k_, v_)
         ms = {c: [] for c in chunks}
         peak = {}
 
         def run(c):
-            cache.reset()
-            return logits_step(m, prompt, cache, prefill_chunk=c).argmax(-1)
+            caches[c[1]].reset()
+            return logits_step(m, prompt, caches[c[1]], prefill_chunk=c[0]).argmax(-1)
 
         for c in chunks:                                    # warm-up: GEMM choices per piece shape
             run(c)
@@ -464,8 +528,8 @@ def prefill_bench(a, m):
                 ms[c].append(_timed(lambda: run(c)))
                 peak[c] = torch.cuda.max_memory_allocated() - base
         for c in chunks:
-            print(json.dumps({"bench": "prefill", "model": a.model, "batch": B, "prompt": a.prompt, "prefill_chunk": c,
-                              "ttft_ms": [round(x, 3) for x in ms[c]], "ttft_ms_median": round(_median(ms[c]), 3),
+            print(json.dumps({"bench": "prefill", "model": a.model, "batch": B, "prompt": a.prompt, "prefill_chunk": c[0],
+                              "weights": forms[c[1]][0], "ttft_ms": [round(x, 3) for x in ms[c]], "ttft_ms_median": round(_median(ms[c]), 3),
                               "peak_bytes_above_cache": peak[c]}), flush=True)
 
 
@@ -506,15 +570,21 @@ def continuation_bench(a, m):
         new = ids[:, a.t0:].contiguous()
         out = {}
 
+        codes = dict(_weight_forms(a, m))                   # --quantised-prefill: "fp8 on", "mxfp4 on" modes
+
         def run(mode):
             cache.len = a.t0                                # the same continuation again
-            G._attention_step = kernel_step if mode == "kernel" else einsum_step
+            G._attention_step = einsum_step if mode == "einsum" else kernel_step
+            for k_, v_ in codes.get(mode, {}).items():
+                setattr(cache, k_, v_)
             try:
                 out[mode] = G.logits_step(m, new, cache)
             finally:
                 G._attention_step = kernel_step
+                cache.w8 = cache.w4 = None
+                cache.wq_prefill = False
 
-        ms = {"kernel": [], "einsum": []}
+        ms = {mode: [] for mode in ["kernel", "einsum"] + [k_ for k_ in codes if k_.endswith(" on")]}
         for mode in ms:
             run(mode)                                       # warm-up
         rel = ((out["kernel"] - out["einsum"]).norm() / out["einsum"].norm()).item()
@@ -524,6 +594,8 @@ def continuation_bench(a, m):
         print(json.dumps({"bench": "continuation", "model": a.model, "batch": B, "t0": a.t0, "chunk": a.chunk,
                           "kernel_ms": [round(x, 3) for x in ms["kernel"]],
                           "einsum_ms": [round(x, 3) for x in ms["einsum"]],
+                          **{k_.replace(" on", "_codes_ms_median"): round(_median(v_), 3) for k_, v_ in ms.items()
+                             if k_.endswith(" on")},
                           "kernel_ms_median": round(_median(ms["kernel"]), 3),
                           "einsum_ms_median": round(_median(ms["einsum"]), 3),
                           "kernel_not_slower_in_any_round": all(k <= e for k, e in zip(ms["kernel"], ms["einsum"])),
