@@ -72,8 +72,15 @@ const int* check_chunk_n(const c10::optional<torch::Tensor>& n, int64_t B, const
 // [0, len[b] + t] of the cache, which already holds the chunk's rows (_kv_append_chunk).  A
 // query with t >= n[b] or len[b] + t >= T_max gives zeros.  Bound with a leading underscore:
 // the module's recorded public surface (tests/golden/ext_api.txt) is left as it is.
-torch::Tensor attn_extend(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor len,
-                          c10::optional<torch::Tensor> n, double scale) {
+// (the checked shape of an extend call: shared by _attn_extend and the bf16 form of _attn_extend_split)
+struct ExtendShape {
+  int64_t B, T, H, hd, Tmax;
+  bool rows;
+  const int* n;
+};
+
+ExtendShape check_extend(const torch::Tensor& q, const torch::Tensor& kc, const torch::Tensor& vc,
+                         const torch::Tensor& len, const c10::optional<torch::Tensor>& n) {
   check_rowmajor(q, "q");
   check_cache(kc, "k_cache");
   check_cache(vc, "v_cache");
@@ -86,11 +93,16 @@ torch::Tensor attn_extend(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
               "attn_extend: q must be bf16 rows [B*T, >= H*hd], row stride % 8 == 0, 16-byte aligned");
   const int64_t T = q.size(0) / B;
   TORCH_CHECK(B * H <= 65535 && B * T * H * hd < (1LL << 31) && Tmax < (1LL << 30), "attn_extend: shape too large");
-  const int* np = check_chunk_n(n, B, q);
+  return {B, T, H, hd, Tmax, rows, check_chunk_n(n, B, q)};
+}
+
+torch::Tensor attn_extend(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor len,
+                          c10::optional<torch::Tensor> n, double scale) {
+  const ExtendShape c = check_extend(q, kc, vc, len, n);
   const at::DeviceGuard g(q.device());
-  auto o = torch::empty({B * T, H * hd}, q.options());
-  dpfs_attn_extend(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(), rows ? 1 : 0, np,
-                   o.data_ptr(), (int)B, (int)T, (int)H, (int)hd, (int)Tmax, (float)scale, stream());
+  auto o = torch::empty({c.B * c.T, c.H * c.hd}, q.options());
+  dpfs_attn_extend(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), len.data_ptr<int>(), c.rows ? 1 : 0, c.n,
+                   o.data_ptr(), (int)c.B, (int)c.T, (int)c.H, (int)c.hd, (int)c.Tmax, (float)scale, stream());
   return o;
 }
 
@@ -371,8 +383,9 @@ torch::Tensor attn_decode_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8
 }
 
 // attn_extend over an fp8 cache (which already holds the chunk's rows, _kv_append_chunk_q8).
-torch::Tensor attn_extend_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8, torch::Tensor ks, torch::Tensor vs,
-                             torch::Tensor len, c10::optional<torch::Tensor> n, double scale) {
+ExtendShape check_extend_q8(const torch::Tensor& q, const torch::Tensor& k8, const torch::Tensor& v8,
+                            const torch::Tensor& ks, const torch::Tensor& vs, const torch::Tensor& len,
+                            const c10::optional<torch::Tensor>& n) {
   check_rowmajor(q, "q");
   const Q8Shape c = check_cache_q8(k8, v8, ks, vs, "attn_extend_q8");
   const bool rows = check_len(len, c.B);
@@ -381,12 +394,47 @@ torch::Tensor attn_extend_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8
               "attn_extend_q8: q must be bf16 rows [B*T, >= H*hd], row stride % 8 == 0, 16-byte aligned");
   const int64_t T = q.size(0) / c.B;
   TORCH_CHECK(c.B * c.H <= 65535 && c.B * T * c.H * c.hd < (1LL << 31), "attn_extend_q8: shape too large");
-  const int* np = check_chunk_n(n, c.B, q);
+  return {c.B, T, c.H, c.hd, c.Tmax, rows, check_chunk_n(n, c.B, q)};
+}
+
+torch::Tensor attn_extend_q8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8, torch::Tensor ks, torch::Tensor vs,
+                             torch::Tensor len, c10::optional<torch::Tensor> n, double scale) {
+  const ExtendShape c = check_extend_q8(q, k8, v8, ks, vs, len, n);
   const at::DeviceGuard g(q.device());
-  auto o = torch::empty({c.B * T, c.H * c.hd}, q.options());
+  auto o = torch::empty({c.B * c.T, c.H * c.hd}, q.options());
   dpfs_attn_extend_q8(q.data_ptr(), q.stride(0), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(),
-                      vs.data_ptr<float>(), len.data_ptr<int>(), rows ? 1 : 0, np, o.data_ptr(), (int)c.B, (int)T,
+                      vs.data_ptr<float>(), len.data_ptr<int>(), c.rows ? 1 : 0, c.n, o.data_ptr(), (int)c.B, (int)c.T,
                       (int)c.H, (int)c.hd, (int)c.Tmax, (float)scale, stream());
+  return o;
+}
+
+// The fp32 workspace of a split extend launch (kernels/attn_extend.hip, ExtSplitArgs): never initialised.
+torch::Tensor extend_split_ws(const torch::Tensor& q, int64_t splits, int64_t B, int64_t T, int64_t H, int64_t hd) {
+  return torch::empty({splits * B * H * T * (hd + 2)}, q.options().dtype(torch::kFloat32));
+}
+
+void check_splits(int64_t splits, const char* op) {
+  TORCH_CHECK(splits >= 1 && splits <= 64, op, ": splits must be in [1, 64], got ", splits);
+}
+
+// _attn_extend (ks / vs none) or _attn_extend_q8 with the key tiles of every 32-query tile cut into
+// `splits` ranges, one workgroup each, and a combine launch behind it (two launches, no atomics, no
+// waiting between workgroups: deterministic).  splits == 1 is the unsplit kernel itself.  Recorded in
+// tests/golden/ext_api_extend_split.txt (tests/test_ext_api_extend_split.py).
+torch::Tensor attn_extend_split(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> ks,
+                                c10::optional<torch::Tensor> vs, torch::Tensor len, c10::optional<torch::Tensor> n,
+                                double scale, int64_t splits) {
+  check_splits(splits, "attn_extend_split");
+  TORCH_CHECK(ks.has_value() == vs.has_value(), "attn_extend_split: ks and vs are given together (fp8 caches) or not at all");
+  if (splits == 1) return ks ? attn_extend_q8(q, kc, vc, *ks, *vs, len, n, scale) : attn_extend(q, kc, vc, len, n, scale);
+  const ExtendShape c = ks ? check_extend_q8(q, kc, vc, *ks, *vs, len, n) : check_extend(q, kc, vc, len, n);
+  const at::DeviceGuard g(q.device());
+  auto o = torch::empty({c.B * c.T, c.H * c.hd}, q.options());
+  auto part = extend_split_ws(q, splits, c.B, c.T, c.H, c.hd);
+  dpfs_attn_extend_split(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), ks ? ks->data_ptr<float>() : nullptr,
+                         ks ? vs->data_ptr<float>() : nullptr, len.data_ptr<int>(), c.rows ? 1 : 0, c.n, o.data_ptr(),
+                         (int)c.B, (int)c.T, (int)c.H, (int)c.hd, (int)c.Tmax, (float)scale, (int)splits,
+                         part.data_ptr<float>(), stream());
   return o;
 }
 
@@ -564,11 +612,26 @@ void kv_append_chunk_paged(torch::Tensor qkv, torch::Tensor kp, torch::Tensor vp
                                (int)T, (int)c.H, (int)c.hd, (int)t_max, stream());
 }
 
+torch::Tensor attn_extend_split_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
+                                      c10::optional<torch::Tensor> ks, c10::optional<torch::Tensor> vs,
+                                      torch::Tensor tbl, torch::Tensor len, c10::optional<torch::Tensor> n,
+                                      int64_t t_max, int64_t page, double scale, int64_t splits);
+
 // _attn_extend / _attn_extend_q8 through a block table (the pools already hold the chunk's rows):
 // the same tiles over the logical key index, bit-identical to the contiguous launch.
 torch::Tensor attn_extend_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, c10::optional<torch::Tensor> ks,
                                 c10::optional<torch::Tensor> vs, torch::Tensor tbl, torch::Tensor len,
                                 c10::optional<torch::Tensor> n, int64_t t_max, int64_t page, double scale) {
+  return attn_extend_split_paged(q, kp, vp, ks, vs, tbl, len, n, t_max, page, scale, 1);
+}
+
+// _attn_extend_paged with `splits` workgroups per 32-query tile (_attn_extend_split through a block
+// table); splits == 1 launches the unsplit kernel, without workspace or combine.
+torch::Tensor attn_extend_split_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
+                                      c10::optional<torch::Tensor> ks, c10::optional<torch::Tensor> vs,
+                                      torch::Tensor tbl, torch::Tensor len, c10::optional<torch::Tensor> n,
+                                      int64_t t_max, int64_t page, double scale, int64_t splits) {
+  check_splits(splits, "attn_extend_split_paged");
   check_rowmajor(q, "q");
   const PagedShape c = check_paged(kp, vp, ks, vs, tbl, len, t_max, page, "attn_extend_paged");
   TORCH_CHECK(q.size(0) % c.B == 0 && q.size(0) >= c.B && q.size(1) >= c.H * c.hd && q.stride(0) % 8 == 0 &&
@@ -579,9 +642,17 @@ torch::Tensor attn_extend_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor
   const int* np = check_chunk_n(n, c.B, q);
   const at::DeviceGuard g(q.device());
   auto o = torch::empty({c.B * T, c.H * c.hd}, q.options());
-  dpfs_attn_extend_paged(q.data_ptr(), q.stride(0), kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(),
-                         (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), np, o.data_ptr(), (int)c.B, (int)T, (int)c.H,
-                         (int)c.hd, (int)t_max, (float)scale, stream());
+  if (splits == 1) {
+    dpfs_attn_extend_paged(q.data_ptr(), q.stride(0), kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(),
+                           (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), np, o.data_ptr(), (int)c.B, (int)T, (int)c.H,
+                           (int)c.hd, (int)t_max, (float)scale, stream());
+    return o;
+  }
+  auto part = extend_split_ws(q, splits, c.B, T, c.H, c.hd);
+  dpfs_attn_extend_split_paged(q.data_ptr(), q.stride(0), kp.data_ptr(), vp.data_ptr(), c.ks, c.vs, tbl.data_ptr<int>(),
+                               (int)c.MP, (int)c.P, c.lg, len.data_ptr<int>(), np, o.data_ptr(), (int)c.B, (int)T,
+                               (int)c.H, (int)c.hd, (int)t_max, (float)scale, (int)splits, part.data_ptr<float>(),
+                               stream());
   return o;
 }
 
@@ -822,6 +893,11 @@ void bind_decode(py::module_& m) {
   m.def("_attn_extend_paged", &attn_extend_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("ks"),
         py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("n"), py::arg("t_max"), py::arg("page"),
         py::arg("scale"));
+  m.def("_attn_extend_split", &attn_extend_split, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("ks"),
+        py::arg("vs"), py::arg("len"), py::arg("n"), py::arg("scale"), py::arg("splits"));
+  m.def("_attn_extend_split_paged", &attn_extend_split_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("ks"), py::arg("vs"), py::arg("tbl"), py::arg("len"), py::arg("n"), py::arg("t_max"), py::arg("page"),
+        py::arg("scale"), py::arg("splits"));
   m.def("fp8_quant", &fp8_quant, py::arg("x"), py::arg("fmt") = 0);
   m.def("gemv_nt_ok", &gemv_nt_ok, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_nt", &gemv_nt, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("swiglu") = false);

@@ -51,6 +51,15 @@ void dpfs_attn_extend_q8(const void* q, long long ldq, const void* k8, const voi
 void dpfs_attn_extend_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
                             const float* vs, const int* tbl, int MP, int P, int lg, const int* len, const int* n,
                             void* o, int B, int T, int H, int HD, int Tmax, float scale, hipStream_t s);
+// split form: the keys of every 32-query tile over S >= 1 workgroups, then a combine launch; ks / vs null: bf16
+// caches / pools, else e4m3 with fp32 scales; part: S * B * H * T * (HD + 2) fp32 of workspace, any content
+void dpfs_attn_extend_split(const void* q, long long ldq, const void* kc, const void* vc, const float* ks,
+                            const float* vs, const int* len, int len_rows, const int* n, void* o, int B, int T, int H,
+                            int HD, int Tmax, float scale, int S, float* part, hipStream_t s);
+void dpfs_attn_extend_split_paged(const void* q, long long ldq, const void* kp, const void* vp, const float* ks,
+                                  const float* vs, const int* tbl, int MP, int P, int lg, const int* len, const int* n,
+                                  void* o, int B, int T, int H, int HD, int Tmax, float scale, int S, float* part,
+                                  hipStream_t s);
 void dpfs_kv_append_chunk_paged(const void* ksrc, const void* vsrc, long long ld, void* kp, void* vp, const int* tbl,
                                 int MP, int P, int lg, const int* len, const int* n, int B, int T, int H, int HD,
                                 int Tmax, hipStream_t s);

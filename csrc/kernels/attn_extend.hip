@@ -38,6 +38,15 @@
 // are pools addressed through a block table.  Tiles, waves and the merge stay on the logical key
 // index; only the K-row and V-chunk fetches differ, each lane looking up the pool row of the key
 // it loads, so the output equals the contiguous launch on the same cache content bit for bit.
+//
+// Split form (SPLIT = true, all four cache forms): a short chunk over a long cache at small batch
+// is ceil(T / 32) * B * H workgroups that each walk every key tile.  Grid z = S cuts a query
+// tile's key tiles into S contiguous ranges; inside its range a workgroup is the kernel above (4
+// waves stride the range, same prefetch, masking, V zeroing, Q8 and PAGED code on the logical key
+// index) and ends by writing its merged, unnormalised fp32 (m, l, O) per query to a workspace.
+// attn_extend_combine_k, a second launch on the same stream, merges the splits in index order and
+// stores the bf16 rows.  No atomics, no flags, no last-workgroup-combines: deterministic, and
+// nothing can wait on a workgroup that is not resident.
 #include "common.h"
 #include "kv8.h"
 #include "kv_page.h"
@@ -57,14 +66,49 @@ __device__ __forceinline__ int ext_swz(int r, int ch) {
   return HD == 64 ? (ch ^ (((r >> 1) & 1) << 2)) : (ch ^ ((r & 3) << 2));
 }
 
-template <int HD, bool Q8 = false, bool PAGED = false, typename... PG>
+// The workspace of the split form, S splits of a launch of B * H (b, h) pairs and T queries:
+//   po  [S][B * H][T][HD] fp32   the split's merged, NOT normalised O row of query t
+//   pml [S][B * H][T][2]  fp32   its running max m (log2 domain, -inf: no key seen) and row sum l
+// S * (queries) * (HD + 2) * 4 bytes in all; the two images are apart so that O rows stay 16-byte
+// aligned.  Which slots a launch writes is a function of len / n alone (ext_split_plan below), and
+// the combine kernel reads exactly those: the workspace needs no initialisation.
+struct ExtSplitArgs {
+  float* po;
+  float* pml;
+};
+
+// The SPLIT form's parameter pack is (ExtSplitArgs, the page arguments of the form); the others'
+// is the page arguments alone, as before the split form existed.
+template <bool PAGED, typename... PG>
+__device__ __forceinline__ KvPageArgs<PAGED> ext_page_args_after(ExtSplitArgs, PG... pgv) {
+  return kv_page_args<PAGED>(pgv...);
+}
+template <bool PAGED, bool SPLIT, typename... PG>
+__device__ __forceinline__ KvPageArgs<PAGED> ext_page_args(PG... pgv) {
+  if constexpr (SPLIT) return ext_page_args_after<PAGED>(pgv...);
+  else return kv_page_args<PAGED>(pgv...);
+}
+template <typename... PG>
+__device__ __forceinline__ ExtSplitArgs ext_split_args(ExtSplitArgs a, PG...) {
+  return a;
+}
+
+// Key tiles per split of a query tile with nkt key tiles under S splits: split s owns tiles
+// [s * tps, min(nkt, (s + 1) * tps)), and splits s >= ceil(nkt / tps) are empty.
+__device__ __forceinline__ int ext_split_tps(int nkt, int S) { return (nkt + S - 1) / S; }
+
+// SPLIT (grid z = S splits): a workgroup takes the key tiles of its split only, out of the row's
+// ACTUAL tiles (nkt comes from len[b], so a short row of a long cache still spreads over the
+// splits), and leaves the merged (m, l, O) of its 32 queries in the workspace; attn_extend_combine_k
+// finishes.  A tile with no live query, and a split whose range is empty, writes nothing.
+template <int HD, bool Q8 = false, bool PAGED = false, bool SPLIT = false, typename... PG>
 __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q, long long ldq,
                                                      const void* __restrict__ kcv, const void* __restrict__ vcv,
                                                      const float* __restrict__ ksc, const float* __restrict__ vsc,
                                                      const int* __restrict__ len_ptr, int len_rows,
                                                      const int* __restrict__ n_ptr, bf16* __restrict__ o, int T,
                                                      int H, int Tmax, float scale, PG... pgv) {
-  const KvPageArgs<PAGED> pg = kv_page_args<PAGED>(pgv...);
+  const KvPageArgs<PAGED> pg = ext_page_args<PAGED, SPLIT>(pgv...);
   constexpr int KS = HD / 16, DTN = HD / 32, RB = HD * 2, CPR = HD / 8;
   constexpr int VT = kExtK * RB;             // a wave's V tile
   constexpr int NVC = kExtK * CPR / 64;      // 16-byte V chunks per lane per tile
@@ -85,6 +129,7 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
   bf16* obase = o + ((long long)b * T) * ((long long)H * HD) + (long long)h * HD;
 
   if (q0 >= nlive) {   // block-uniform: nothing to attend, the tile's rows are zeros
+    if constexpr (SPLIT) return;   // (the combine kernel stores them)
     const int qq = threadIdx.x >> 3, part = threadIdx.x & 7;
     if (q0 + qq < T) {
       bf16* orow = obase + (long long)(q0 + qq) * H * HD + part * (HD / 8);
@@ -96,6 +141,15 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
   }
   const int kmax = len + min(q0 + kExtQ, nlive) - 1;   // last key any query of the tile attends (< Tmax)
   const int nkt = kmax / kExtK + 1;
+  // the wave's key tiles kt0, kt0 + 4, ... < kte: all of the tile's, or with SPLIT those of split
+  // blockIdx.z (block-uniform; an empty split leaves before the first barrier)
+  int kt0 = wave, kte = nkt;
+  if constexpr (SPLIT) {
+    const int tps = ext_split_tps(nkt, (int)gridDim.z);
+    if ((int)blockIdx.z * tps >= nkt) return;
+    kt0 = (int)blockIdx.z * tps + wave;
+    kte = min(nkt, ((int)blockIdx.z + 1) * tps);
+  }
   const float c2 = scale * kLog2e;
 
   // Q^T operand: lane holds Q[q0 + r32][16 ks + 8 hf + j]; zeros for a query that is not live
@@ -188,8 +242,8 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
     for (int i = 0; i < 16; ++i) oacc[d][i] = 0.f;
   float m = -INFINITY, lsum = 0.f;
 
-  if (wave < nkt) fetch(wave);
-  for (int kt = wave; kt < nkt; kt += 4) {
+  if (kt0 < kte) fetch(kt0);
+  for (int kt = kt0; kt < kte; kt += 4) {
     const int k0 = kt * kExtK;
     // this tile's V into the wave's LDS region (the wave's earlier reads of it have returned:
     // their values fed the MFMAs above); LDS serves a wave's operations in order
@@ -210,7 +264,7 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    if (kt + 4 < nkt) fetch(kt + 4);   // the next tile's loads fly under this tile's math
+    if (kt + 4 < kte) fetch(kt + 4);   // the next tile's loads fly under this tile's math
 
     f32x16 s;
 #pragma unroll
@@ -296,6 +350,14 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
     const bool lq = t < nlive;
     const float inv = lq ? 1.f / ls : 0.f;
     bf16* orow = obase + (long long)t * H * HD + part * (HD / 8);
+    // SPLIT: the merged partial relative to M, not normalised, goes to slot (split, b h, t); a
+    // query that is not live or sees no key of this split leaves (m, l, O) = (-inf, 0, 0)
+    long long slot = 0;
+    float* prow = nullptr;
+    if constexpr (SPLIT) {
+      slot = ((long long)blockIdx.z * gridDim.y + bh) * T + t;
+      prow = ext_split_args(pgv...).po + slot * HD + part * (HD / 8);
+    }
 #pragma unroll
     for (int c = 0; c < HD / 32; ++c) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -305,10 +367,71 @@ __global__ __launch_bounds__(256) void attn_extend_k(const bf16* __restrict__ q,
                                                         ((long long)w * kExtQ + qq) * OLD + part * (HD / 8) + 4 * c);
         acc += f[w] * v;
       }
-      bf16x4 r = {};
-      if (lq) r = (bf16x4){(bf16)(acc[0] * inv), (bf16)(acc[1] * inv), (bf16)(acc[2] * inv), (bf16)(acc[3] * inv)};
-      *reinterpret_cast<bf16x4*>(orow + 4 * c) = r;
+      if constexpr (SPLIT) {
+        *reinterpret_cast<f32x4*>(prow + 4 * c) = acc;
+      } else {
+        bf16x4 r = {};
+        if (lq) r = (bf16x4){(bf16)(acc[0] * inv), (bf16)(acc[1] * inv), (bf16)(acc[2] * inv), (bf16)(acc[3] * inv)};
+        *reinterpret_cast<bf16x4*>(orow + 4 * c) = r;
+      }
     }
+    if constexpr (SPLIT) {
+      if (part == 0) *reinterpret_cast<f32x2*>(ext_split_args(pgv...).pml + 2 * slot) = (f32x2){M, ls};
+    }
+  }
+}
+
+// The second launch of the split form: grid (ceil(T / 32), B * H), thread = (query, HD / 8 output
+// columns) as in attn_extend_k's merge.  It works out from len / n which splits of its tile wrote
+// a partial (those with a non-empty tile range: s < ceil(nkt / tps)) and reads only those, in
+// index order: M = max m_s, f_s = exp2(m_s - M) (0 for -inf), sum f_s l_s and sum f_s O_s, one
+// reciprocal, one bf16 rounding.  Rows that are not live, and tiles without a live query (which no
+// split touched), are stored as zeros.
+template <int HD>
+__global__ __launch_bounds__(256) void attn_extend_combine_k(const float* __restrict__ po,
+                                                             const float* __restrict__ pml,
+                                                             const int* __restrict__ len_ptr, int len_rows,
+                                                             const int* __restrict__ n_ptr, bf16* __restrict__ o,
+                                                             int T, int H, int Tmax, int S) {
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int q0 = blockIdx.x * kExtQ;
+  const int qq = threadIdx.x >> 3, part = threadIdx.x & 7;
+  const int t = q0 + qq;
+  if (t >= T) return;
+  const int len = len_ptr[len_rows ? b : 0];
+  const int nb = n_ptr ? min(max(n_ptr[b], 0), T) : T;
+  const int nlive = len < 0 ? 0 : min(nb, Tmax - len);
+  bf16* orow = o + ((long long)b * T + t) * ((long long)H * HD) + (long long)h * HD + part * (HD / 8);
+  f32x4 acc[HD / 32];
+#pragma unroll
+  for (int c = 0; c < HD / 32; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float ls = 0.f;
+  const bool lq = t < nlive;
+  if (lq) {   // (then q0 < nlive: the tile's splits ran)
+    const int kmax = len + min(q0 + kExtQ, nlive) - 1;
+    const int nkt = kmax / kExtK + 1;
+    const int tps = ext_split_tps(nkt, S);
+    const int ns = (nkt + tps - 1) / tps;       // the splits that wrote: 1 <= ns <= S
+    const long long sstride = (long long)gridDim.y * T;   // slots per split
+    const long long slot0 = (long long)bh * T + t;
+    float M = -INFINITY;
+    for (int s = 0; s < ns; ++s) M = fmaxf(M, pml[2 * (slot0 + s * sstride)]);
+    for (int s = 0; s < ns; ++s) {
+      const long long slot = slot0 + s * sstride;
+      const f32x2 ml = *reinterpret_cast<const f32x2*>(pml + 2 * slot);
+      const float f = ml[0] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ml[0] - M);
+      ls += f * ml[1];
+      const float* prow = po + slot * HD + part * (HD / 8);
+#pragma unroll
+      for (int c = 0; c < HD / 32; ++c) acc[c] += f * *reinterpret_cast<const f32x4*>(prow + 4 * c);
+    }
+  }
+  const float inv = lq ? 1.f / ls : 0.f;
+#pragma unroll
+  for (int c = 0; c < HD / 32; ++c) {
+    bf16x4 r = {};
+    if (lq) r = (bf16x4){(bf16)(acc[c][0] * inv), (bf16)(acc[c][1] * inv), (bf16)(acc[c][2] * inv), (bf16)(acc[c][3] * inv)};
+    *reinterpret_cast<bf16x4*>(orow + 4 * c) = r;
   }
 }
 
@@ -419,6 +542,72 @@ extern "C" void dpfs_attn_extend_paged(const void* q, long long ldq, const void*
     else EXT_LAUNCH(128, false);
   }
 #undef EXT_LAUNCH
+}
+
+// ------------------------------------------------------------------------- split form --
+// S >= 1 splits of every query tile's keys, then the combine: two launches on the stream, no
+// atomics and nothing that waits on another workgroup.  part: S * B * H * T * (HD + 2) fp32 of
+// workspace (ExtSplitArgs), which may hold anything.
+static ExtSplitArgs ext_split_ws(float* part, int S, int B, int T, int H, int HD) {
+  return {part, part + (long long)S * B * H * T * HD};
+}
+
+static void ext_combine(const ExtSplitArgs& ws, const int* len, int len_rows, const int* n, void* o, int B, int T,
+                        int H, int HD, int Tmax, int S, hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H);
+#define EXT_COMBINE(HD_) \
+  attn_extend_combine_k<HD_><<<grid, 256, 0, s>>>(ws.po, ws.pml, len, len_rows, n, (bf16*)o, T, H, Tmax, S)
+  if (HD == 32) EXT_COMBINE(32);
+  else if (HD == 64) EXT_COMBINE(64);
+  else EXT_COMBINE(128);
+#undef EXT_COMBINE
+}
+
+// dpfs_attn_extend (ks / vs null) or dpfs_attn_extend_q8 with the keys of a query tile over S workgroups.
+extern "C" void dpfs_attn_extend_split(const void* q, long long ldq, const void* kc, const void* vc, const float* ks,
+                                       const float* vs, const int* len, int len_rows, const int* n, void* o, int B,
+                                       int T, int H, int HD, int Tmax, float scale, int S, float* part,
+                                       hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H, S);
+  const ExtSplitArgs ws = ext_split_ws(part, S, B, T, H, HD);
+#define EXT_LAUNCH(HD_, Q8_)                                                                                    \
+  attn_extend_k<HD_, Q8_, false, true><<<grid, 256, 0, s>>>((const bf16*)q, ldq, kc, vc, ks, vs, len, len_rows, n, \
+                                                            (bf16*)o, T, H, Tmax, scale, ws)
+  if (ks) {
+    if (HD == 32) EXT_LAUNCH(32, true);
+    else if (HD == 64) EXT_LAUNCH(64, true);
+    else EXT_LAUNCH(128, true);
+  } else {
+    if (HD == 32) EXT_LAUNCH(32, false);
+    else if (HD == 64) EXT_LAUNCH(64, false);
+    else EXT_LAUNCH(128, false);
+  }
+#undef EXT_LAUNCH
+  ext_combine(ws, len, len_rows, n, o, B, T, H, HD, Tmax, S, s);
+}
+
+// dpfs_attn_extend_paged likewise.
+extern "C" void dpfs_attn_extend_split_paged(const void* q, long long ldq, const void* kp, const void* vp,
+                                             const float* ks, const float* vs, const int* tbl, int MP, int P, int lg,
+                                             const int* len, const int* n, void* o, int B, int T, int H, int HD,
+                                             int Tmax, float scale, int S, float* part, hipStream_t s) {
+  const dim3 grid((T + kExtQ - 1) / kExtQ, B * H, S);
+  const ExtSplitArgs ws = ext_split_ws(part, S, B, T, H, HD);
+  const KvPageArgs<true> pg{tbl, MP, P, lg};
+#define EXT_LAUNCH(HD_, Q8_)                                                                                       \
+  attn_extend_k<HD_, Q8_, true, true><<<grid, 256, 0, s>>>((const bf16*)q, ldq, kp, vp, ks, vs, len, 1, n, (bf16*)o, T, \
+                                                           H, Tmax, scale, ws, pg)
+  if (ks) {
+    if (HD == 32) EXT_LAUNCH(32, true);
+    else if (HD == 64) EXT_LAUNCH(64, true);
+    else EXT_LAUNCH(128, true);
+  } else {
+    if (HD == 32) EXT_LAUNCH(32, false);
+    else if (HD == 64) EXT_LAUNCH(64, false);
+    else EXT_LAUNCH(128, false);
+  }
+#undef EXT_LAUNCH
+  ext_combine(ws, len, 1, n, o, B, T, H, HD, Tmax, S, s);
 }
 
 // dpfs_kv_append_chunk into bf16 pools (the fp8 form is dpfs_kv_append_chunk_q8_paged, kv8.hip).

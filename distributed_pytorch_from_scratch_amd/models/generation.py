@@ -526,6 +526,39 @@ def _attention_step(layer, x2d, positions, tab, cache: KVCache, li: int, B: int,
     return attn.wo(_attend(qkv, h, hd, positions, tab, cache, li, B, T, n_t))
 
 
+# The split form of the extend attention (``_attn_extend_split``): the grid is filled to
+# _EXT_FILL workgroups per CU, and a split is given at least _EXT_MIN_TILES 32-key tiles of a full
+# cache.  The sweep behind the two is profiles/extend_split_bench.jsonl (README, "Prefill against a
+# cache"): 2 workgroups per CU lost to the unsplit launch at head_dim 128, where one is resident.
+_EXT_FILL = 1
+_EXT_MIN_TILES = 32
+_EXT_MAX_SPLITS = 64
+_CUS = {}
+
+
+def _extend_splits(T: int, B: int, h: int, t_max: int, cus: int) -> int:
+    """Splits S of a (B, T) extend launch over ``h`` local heads and a cache of capacity ``t_max`` on
+    ``cus`` compute units, from host values alone (no device read, nothing synchronises; the kernel
+    divides every row's actual keys by S).  ``DPFS_EXTEND_SPLIT``, read per call: ``auto`` (default),
+    ``0`` (never split) or an integer (that S, clamped to [1, 64])."""
+    env = os.environ.get("DPFS_EXTEND_SPLIT", "auto").strip().lower()
+    if env != "auto":
+        return max(1, min(int(env), _EXT_MAX_SPLITS))
+    grid = -(-T // 32) * B * h
+    return max(1, min(_EXT_FILL * cus // grid, -(-t_max // 32) // _EXT_MIN_TILES, _EXT_MAX_SPLITS))
+
+
+def _extend_splits_for(qkv, h: int, B: int, T: int, t_max: int) -> int:
+    """``_extend_splits`` for the device and dtype of ``qkv``: 1 off the GPU and for fp32 compute, whose
+    extend attention is the tensor-op path."""
+    if not qkv.is_cuda or qkv.dtype != torch.bfloat16:
+        return 1
+    cus = _CUS.get(qkv.device.index)
+    if cus is None:
+        cus = _CUS[qkv.device.index] = torch.cuda.get_device_properties(qkv.device).multi_processor_count
+    return _extend_splits(T, B, h, t_max, cus)
+
+
 def _attend(qkv, h: int, hd: int, positions, tab, cache: KVCache, li: int, B: int, T: int, n_t=None):
     """RoPE, cache append and attention of a multi-token step (prefill, or T > 1 continuation) on the
     packed ``qkv`` rows (B*T, 3*h*hd), with host-side cache bookkeeping; returns o (B*T, h*hd).  The
@@ -552,6 +585,8 @@ def _attend(qkv, h: int, hd: int, positions, tab, cache: KVCache, li: int, B: in
             kk = qkv[:, h * hd: 2 * h * hd].view(B, T, h, hd)
             v = qkv[:, 2 * h * hd:].view(B, T, h, hd)
             o, _ = k_.attn_fwd(q, kk, v, scale, True)
+        elif (S := _extend_splits_for(qkv, h, B, T, cache.t_max)) > 1:
+            o = k_._attn_extend_split_paged(qkv, *pools, n_t, cache.t_max, cache.page, scale, S)
         else:
             o = k_._attn_extend_paged(qkv, *pools, n_t, cache.t_max, cache.page, scale)
     elif cache.len == 0:
@@ -567,12 +602,21 @@ def _attend(qkv, h: int, hd: int, positions, tab, cache: KVCache, li: int, B: in
         o, _ = k_.attn_fwd(q, kk, v, scale, True)
     elif cache.fp8:
         k_._kv_append_chunk_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t)
-        o = k_._attn_extend_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t, scale)
+        if (S := _extend_splits_for(qkv, h, B, T, cache.t_max)) > 1:
+            o = k_._attn_extend_split(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t,
+                                      scale, S)
+        else:
+            o = k_._attn_extend_q8(qkv, cache.k[li], cache.v[li], cache.ks[li], cache.vs[li], cache.len_t, n_t, scale)
     else:
         # continuation chunk: every row appends its new keys / values at its own cache length,
-        # then its T new queries attend the cached prefix plus the causal part of the chunk
+        # then its T new queries attend the cached prefix plus the causal part of the chunk; a
+        # short chunk over a long cache at small batch splits every query tile's keys over
+        # workgroups (``_extend_splits``)
         k_._kv_append_chunk(qkv, cache.k[li], cache.v[li], cache.len_t, n_t)
-        o = k_._attn_extend(qkv, cache.k[li], cache.v[li], cache.len_t, n_t, scale)
+        if (S := _extend_splits_for(qkv, h, B, T, cache.t_max)) > 1:
+            o = k_._attn_extend_split(qkv, cache.k[li], cache.v[li], None, None, cache.len_t, n_t, scale, S)
+        else:
+            o = k_._attn_extend(qkv, cache.k[li], cache.v[li], cache.len_t, n_t, scale)
     return o.reshape(B * T, h * hd)
 
 

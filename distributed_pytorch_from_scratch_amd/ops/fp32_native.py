@@ -126,6 +126,9 @@ _kv_append_chunk_paged = reference._kv_append_chunk_paged
 _rope_append_paged = reference._rope_append_paged
 _attn_decode_paged = reference._attn_decode_paged
 _attn_extend_paged = reference._attn_extend_paged
+# (no split form for fp32 caches: the oracle's, which ignores ``splits``)
+_attn_extend_split = reference._attn_extend_split
+_attn_extend_split_paged = reference._attn_extend_split_paged
 gemv_nt = reference.gemv_nt
 
 

@@ -434,6 +434,23 @@ def _attn_extend_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tens
     return _attn_extend_q8(q, kc, vc, _paged_view(ks, tbl, t_max), _paged_view(vs, tbl, t_max), len, n, scale)
 
 
+def _attn_extend_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, ks: Optional[torch.Tensor],
+                       vs: Optional[torch.Tensor], len: torch.Tensor, n: Optional[torch.Tensor], scale: float,
+                       splits: int) -> torch.Tensor:
+    """``_attn_extend`` / ``_attn_extend_q8``: ``splits`` divides the GPU kernel's work, not the result."""
+    if ks is None:
+        return _attn_extend(q, k_cache, v_cache, len, n, scale)
+    return _attn_extend_q8(q, k_cache, v_cache, ks, vs, len, n, scale)
+
+
+def _attn_extend_split_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, ks: Optional[torch.Tensor],
+                             vs: Optional[torch.Tensor], tbl: torch.Tensor, len: torch.Tensor,
+                             n: Optional[torch.Tensor], t_max: int, page: int, scale: float,
+                             splits: int) -> torch.Tensor:
+    """``_attn_extend_paged``, whatever ``splits``."""
+    return _attn_extend_paged(q, k_pool, v_pool, ks, vs, tbl, len, n, t_max, page, scale)
+
+
 def gemv_nt_ok(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> bool:
     return True
 

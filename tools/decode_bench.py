@@ -67,6 +67,10 @@ codes, with ``quantised_prefill`` off (the prefill on bf16 weights) and on (ever
 the same interleaved rounds.  ``--wq-kernel`` times the quantised-weight GEMM launch alone
 (``_gemm_nt_w8`` / ``_gemm_nt_w4``, csrc/kernels/gemm_wq.hip) against ``gemm_nt`` on the bf16 weight, on the
 preset's projection shapes at every ``--batch`` M (``wq_kernel_bench``).
+
+``--continuation --extend-split 0 auto N ...`` times the extend-attention launch alone, unsplit against the
+split form (``_attn_extend_split``) at the rule's and at forced split counts, over short chunks and long
+caches on the GPT-2 small and 7B head shapes (``extend_split_bench``).
 """
 from __future__ import annotations
 
@@ -101,6 +105,9 @@ def main():
     ap.add_argument("--continuation", action="store_true", help="time one multi-token continuation")
     ap.add_argument("--t0", type=int, default=1024, help="--continuation: ids in the cache")
     ap.add_argument("--chunk", type=int, default=256, help="--continuation: new ids")
+    ap.add_argument("--extend-split", nargs="+", default=None, metavar="S",
+                    help="--continuation: time the extend-attention launch alone at these split counts "
+                         "(0: unsplit, auto: the selection rule, N: forced)")
     ap.add_argument("--kv-dtype", choices=["act", "fp8", "both"], default="act",
                     help="KV cache storage: activation dtype, fp8 codes, or both in interleaved rounds")
     ap.add_argument("--modes", nargs="+", choices=["graph", "eager"], default=["graph", "eager"])
@@ -120,7 +127,7 @@ def main():
     ap.add_argument("--wq-kernel", action="store_true",
                     help="time the quantised-weight GEMM launches (gemm_wq.hip) against gemm_nt at every --batch M")
     a = ap.parse_args()
-    if a.kv_page and not a.ragged:
+    if a.kv_page and not (a.ragged or a.extend_split):
         ap.error("--kv-page runs the ragged decode benchmark: give --ragged")
     pen_kw = {}
     if a.penalties:
@@ -154,6 +161,8 @@ def main():
         return w8_kernel_bench(a, args)
     if a.wq_kernel:
         return wq_kernel_bench(a, args)
+    if a.continuation and a.extend_split:
+        return extend_split_bench(a)
     if a.continuation and a.t0 + a.chunk > args.maxlen:     # the RoPE table must cover the continuation
         args = get_preset(a.model, maxlen=a.t0 + a.chunk)
     m = Transformer.from_args(args).cuda()
@@ -600,6 +609,93 @@ def continuation_bench(a, m):
                           "einsum_ms_median": round(_median(ms["einsum"]), 3),
                           "kernel_not_slower_in_any_round": all(k <= e for k, e in zip(ms["kernel"], ms["einsum"])),
                           "logits_rel_diff": rel}), flush=True)
+
+
+# --continuation --extend-split: (name, local heads, head_dim), chunk lengths and cache lengths of the sweep
+EXT_SPLIT_SHAPES = (("gpt2-small", 12, 64), ("7b-heads", 32, 128))
+EXT_SPLIT_CHUNKS = (8, 32, 256)
+EXT_SPLIT_T0 = (4096, 16384, 32768)
+
+
+def extend_split_bench(a):
+    """``--continuation --extend-split 0 auto N ...``: the extend-attention launch alone, a ``chunk``-token
+    step over a cache that holds ``t0`` keys (capacity t0 + 256), on the head shapes of ``EXT_SPLIT_SHAPES``
+    at every ``--batch``, for the bf16 and the fp8 cache and the bf16 paged cache (``--kv-page``, first
+    value, default 64).  Every mode is a split count: ``0`` is the unsplit kernel (``_attn_extend`` and kin,
+    the yardstick), ``auto`` what ``generation._extend_splits`` picks, N that many splits.  One process,
+    ``--repeats`` interleaved rounds, us per launch from device events over a window of launches; one JSON
+    line per case with every mode's rounds, median and spread (max - min), and ``auto_ok``: auto's median is
+    not above the unsplit median by more than the unsplit rounds' spread."""
+    import torch
+    from distributed_pytorch_from_scratch_amd.models import generation as G
+    from distributed_pytorch_from_scratch_amd.ops import _ext
+    C = _ext.require()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    page = (a.kv_page or [64])[0]
+    f8 = torch.float8_e4m3fn
+
+    def splits_of(mode, T, B, h, t_max):
+        os.environ["DPFS_EXTEND_SPLIT"] = mode
+        try:
+            return G._extend_splits(T, B, h, t_max, cus)
+        finally:
+            del os.environ["DPFS_EXTEND_SPLIT"]
+
+    for name, h, hd in EXT_SPLIT_SHAPES:
+        for B in a.batch:
+            for t0 in EXT_SPLIT_T0:
+                t_max = t0 + 256
+                kc = torch.randn(B, t_max, h, hd, device="cuda", dtype=torch.bfloat16)
+                vc = torch.randn(B, t_max, h, hd, device="cuda", dtype=torch.bfloat16)
+                k8 = torch.randint(0, 0x78, (B, t_max, h, hd), device="cuda", dtype=torch.uint8).view(f8)
+                v8 = torch.randint(0, 0x78, (B, t_max, h, hd), device="cuda", dtype=torch.uint8).view(f8)
+                ks = torch.rand(B, t_max, h, device="cuda") * 0.01 + 0.001
+                vs = torch.rand(B, t_max, h, device="cuda") * 0.01 + 0.001
+                ln = torch.full((B,), t0, dtype=torch.int32, device="cuda")
+                mp = -(-t_max // page)
+                tbl = torch.randperm(B * mp, device="cuda").to(torch.int32).view(B, mp)
+                pools = [torch.randn(B * mp, page, h, hd, device="cuda", dtype=torch.bfloat16) for _ in range(2)]
+                for T in EXT_SPLIT_CHUNKS:
+                    q = torch.randn(B * T, 3 * h * hd, device="cuda", dtype=torch.bfloat16)[:, : h * hd]
+                    scale = hd ** -0.5
+                    forms = {
+                        "bf16": lambda S: (C._attn_extend(q, kc, vc, ln, None, scale) if S == 1 else
+                                           C._attn_extend_split(q, kc, vc, None, None, ln, None, scale, S)),
+                        "fp8": lambda S: (C._attn_extend_q8(q, k8, v8, ks, vs, ln, None, scale) if S == 1 else
+                                          C._attn_extend_split(q, k8, v8, ks, vs, ln, None, scale, S)),
+                        f"paged{page}": lambda S: (
+                            C._attn_extend_paged(q, *pools, None, None, tbl, ln, None, t_max, page, scale) if S == 1 else
+                            C._attn_extend_split_paged(q, *pools, None, None, tbl, ln, None, t_max, page, scale, S)),
+                    }
+                    modes = {mode: splits_of(mode, T, B, h, t_max) for mode in a.extend_split}
+                    for form, launch in forms.items():
+                        launch(1)
+                        torch.cuda.synchronize()
+                        one = _timed(lambda: launch(1))                      # ms: sizes the window (>= 2 ms, 5..200 launches)
+                        iters = max(5, min(200, int(2.0 / max(one, 0.01))))
+                        us = {mode: [] for mode in modes}
+                        for mode, S in modes.items():
+                            launch(S)                                        # warm-up
+                        for _ in range(a.repeats):
+                            for mode, S in modes.items():
+                                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                                e0.record()
+                                for _i in range(iters):
+                                    launch(S)
+                                e1.record()
+                                torch.cuda.synchronize()
+                                us[mode].append(1000 * e0.elapsed_time(e1) / iters)
+                        line = {"bench": "extend_split", "shape": name, "heads": h, "head_dim": hd, "batch": B, "t0": t0,
+                                "chunk": T, "cache": form, "cus": cus, "fill": G._EXT_FILL,
+                                "min_tiles": G._EXT_MIN_TILES, "launches_per_round": iters}
+                        for mode, S in modes.items():
+                            line[mode] = {"splits": S, "us": [round(x, 2) for x in us[mode]],
+                                          "median": round(_median(us[mode]), 2),
+                                          "spread": round(max(us[mode]) - min(us[mode]), 2)}
+                        if "0" in modes and "auto" in modes and modes["auto"] > 1:
+                            line["auto_ok"] = line["auto"]["median"] <= line["0"]["median"] + line["0"]["spread"]
+                        print(json.dumps(line), flush=True)
+                del kc, vc, k8, v8, ks, vs, pools
 
 
 def sample_kernel_bench(a, ld: int, vocab: int):
