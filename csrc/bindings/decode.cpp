@@ -309,6 +309,55 @@ torch::Tensor gemm_nt_w4(torch::Tensor x, torch::Tensor codes, torch::Tensor sca
   return y;
 }
 
+// ------------------------------------------ fp8 activations on fp8 weights, any M (prefill) --
+// W8A8 (kernels/gemm_w8a8.hip): per-token e4m3 activation codes xc uint8 [M, K] with one fp32 scale sa [M]
+// (the rows of _quant_w8_rows / _swiglu_quant_w8_rows) on the session's weight codes, on the fp8 MFMA.
+// Recorded in tests/golden/ext_api_w8a8.txt (tests/test_ext_api_w8a8.py).
+bool gemm_nt_w8a8_ok(torch::Tensor xc, torch::Tensor codes) {
+  if (!xc.is_cuda() || !codes.is_cuda() || xc.dim() != 2 || codes.dim() != 2 || xc.scalar_type() != torch::kUInt8 ||
+      codes.scalar_type() != torch::kUInt8 || xc.stride(1) != 1 || codes.stride(1) != 1 ||
+      xc.device() != codes.device())
+    return false;
+  const int64_t K = codes.size(1);
+  if (xc.size(1) != K || xc.size(0) >= (1LL << 31) || codes.size(0) >= (1LL << 31) || K >= (1LL << 31)) return false;
+  if (reinterpret_cast<uintptr_t>(xc.data_ptr()) % 16 || reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16)
+    return false;   // 16-byte LDS-DMA pieces
+  return dpfs_gemm_w8a8_ok((int)xc.size(0), (int)codes.size(0), (int)K, xc.stride(0), codes.stride(0)) != 0;
+}
+
+// y[M, N] = bf16((xc codes^T) * sa[m] * inv[n] + bias) for any M >= 1, fp32 accumulation of the e4m3 products.
+torch::Tensor gemm_nt_w8a8(torch::Tensor xc, torch::Tensor sa, torch::Tensor codes, torch::Tensor inv,
+                           c10::optional<torch::Tensor> bias) {
+  TORCH_CHECK(gemm_nt_w8a8_ok(xc, codes),
+              "gemm_nt_w8a8: needs uint8 row-major codes xc [M >= 1, K] and codes [N >= 1, K] (row strides % 16 == 0) "
+              "on one device, both 16-byte aligned, K % 128 == 0");
+  const int64_t M = xc.size(0), N = codes.size(0), K = codes.size(1);
+  const at::DeviceGuard g(xc.device());
+  auto y = torch::empty({M, N}, xc.options().dtype(torch::kBFloat16));
+  dpfs_gemm_w8a8(xc.data_ptr(), xc.stride(0), opt_f32(sa, M, "sa"), codes.data_ptr(), codes.stride(0),
+                 opt_f32(inv, N, "inv"), opt_f32(bias, N, "bias"), y.data_ptr(), N, (int)M, (int)N, (int)K, stream());
+  return y;
+}
+
+// (codes uint8 [M, F], inv fp32 [M]) of the rows bf16(silu(gate) * up) of a packed bf16 gu = [gate | up]
+// [M, 2F]: the bytes of _quant_w8_rows(swiglu_fwd(gu)), the F-wide activation never written.
+std::vector<torch::Tensor> swiglu_quant_w8_rows(torch::Tensor gu) {
+  check_cuda(gu, "gu");
+  TORCH_CHECK(gu.dim() == 2 && gu.scalar_type() == torch::kBFloat16 && gu.stride(1) == 1 && gu.size(1) % 16 == 0 &&
+                  gu.size(1) > 0 && (gu.size(0) <= 1 || (gu.stride(0) % 8 == 0 && gu.stride(0) >= gu.size(1))) &&
+                  reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0 && gu.size(0) < (1LL << 31) &&
+                  gu.size(1) < (1LL << 31),
+              "swiglu_quant_w8_rows: gu must be a 16-byte aligned bf16 [M, 2F] with unit column stride, F % 8 == 0 and "
+              "a row stride % 8 == 0");
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  const at::DeviceGuard g(gu.device());
+  auto codes = torch::empty({M, F}, gu.options().dtype(torch::kUInt8));
+  auto inv = torch::empty({M}, gu.options().dtype(torch::kFloat32));
+  dpfs_swiglu_quant_w8_rows(gu.data_ptr(), gu.stride(0), codes.data_ptr(), F, inv.data_ptr<float>(), (int)M, (int)F,
+                            stream());
+  return {codes, inv};
+}
+
 // rope_ on the q and k heads of the packed qkv rows + kv_append of the rotated k and v rows
 // at *len, one kernel (decode step).
 void rope_append(torch::Tensor qkv, torch::Tensor pos, torch::Tensor table, torch::Tensor kc, torch::Tensor vc,
@@ -913,6 +962,10 @@ void bind_decode(py::module_& m) {
   m.def("_gemm_nt_w8", &gemm_nt_w8, py::arg("x"), py::arg("codes"), py::arg("inv"), py::arg("bias") = py::none());
   m.def("_gemm_nt_w4_ok", &gemm_nt_w4_ok, py::arg("x"), py::arg("codes"));
   m.def("_gemm_nt_w4", &gemm_nt_w4, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none());
+  m.def("_gemm_nt_w8a8_ok", &gemm_nt_w8a8_ok, py::arg("xc"), py::arg("codes"));
+  m.def("_gemm_nt_w8a8", &gemm_nt_w8a8, py::arg("xc"), py::arg("sa"), py::arg("codes"), py::arg("inv"),
+        py::arg("bias") = py::none());
+  m.def("_swiglu_quant_w8_rows", &swiglu_quant_w8_rows, py::arg("gu"));
   m.def("rope_append", &rope_append, py::arg("qkv"), py::arg("pos"), py::arg("table"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("len"));
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"),

@@ -263,6 +263,13 @@ int dpfs_gemm_wq4_ok(int M, int N, int K, long long lda, long long ldc, long lon
 void dpfs_gemm_wq4(const void* A, long long lda, const void* codes, long long ldc, const void* scales,
                    long long lds, const float* bias, void* Y, long long ldy, int M, int N, int K, hipStream_t s);
 
+// kernels/gemm_w8a8.hip
+// W8A8 GEMM for any M on the fp8 MFMA: e4m3 activation codes [M, K] (row stride lda bytes) with one fp32
+// scale sa [M] per token row, on the weight codes and inv of gemv_w8.hip; K % 128 == 0
+int dpfs_gemm_w8a8_ok(int M, int N, int K, long long lda, long long ldc);
+void dpfs_gemm_w8a8(const void* acodes, long long lda, const float* sa, const void* codes, long long ldc,
+                    const float* inv, const float* bias, void* Y, long long ldy, int M, int N, int K, hipStream_t s);
+
 // kernels/gemv_w4.hip
 // weight-only MXFP4 decode projections: e2m1 codes [N, K / 2] (row stride ldc bytes, low nibble
 // first) with e8m0 scales [N, K / 32] (row stride lds bytes), K % 128 == 0
@@ -280,6 +287,8 @@ void dpfs_gemv_w8(const void* A, long long lda, const void* codes, long long ldc
                   const float* bias, void* Y, long long ldy, int M, int N, int K, int swiglu, hipStream_t s);
 void dpfs_quant_w8_rows(const void* W, long long ldw, void* codes, long long ldc, float* inv, int N, int K,
                         hipStream_t s);
+void dpfs_swiglu_quant_w8_rows(const void* gu, long long ldg, void* codes, long long ldc, float* inv, int M, int F,
+                               hipStream_t s);
 
 // kernels/kv8.hip
 void dpfs_kv_append_chunk_q8(const void* ksrc, const void* vsrc, long long ld, void* k8, void* v8, float* ks,

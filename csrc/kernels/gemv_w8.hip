@@ -6,6 +6,8 @@
 //
 //   quant_w8_rows_k  one workgroup per weight row: an amax pass over the bf16 row, then the encode
 //                    pass (kv8_scale / kv8_amax8 / kv8_enc8: the bytes of the PyTorch oracle).
+//   swiglu_quant_w8_rows_k  the same on the rows of bf16(silu(g) * u) of a packed [g | u]: the per-token
+//                    activation codes of the W8A8 down projection (gemm_w8a8.hip).
 //   gemv_w8_k        y[M, N] = bf16( fp32(sum_k a[m,k] f32(code[n,k])) * inv[n] + bias[n] ),
 //                    1 <= M <= 64, K % 64 == 0.
 //
@@ -55,6 +57,36 @@ __global__ __launch_bounds__(256) void quant_w8_rows_k(const bf16* __restrict__ 
 }
 
 __device__ __forceinline__ float silu_w8(float g) { return g * __builtin_amdgcn_rcpf(1.f + __expf(-g)); }   // = silu_f
+
+// 8 elements of h = bf16(silu(g) * u): swiglu_fwd_k's formula and rounding
+__device__ __forceinline__ bf16x8 swiglu8_w8(const bf16* g, const bf16* u) {
+  const bf16x8 gv = *reinterpret_cast<const bf16x8*>(g), uv = *reinterpret_cast<const bf16x8*>(u);
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (bf16)(silu_w8((float)gv[j]) * (float)uv[j]);
+  return r;
+}
+
+// quant_w8_rows_k on the rows of h = bf16(silu(g) * u) of a packed gu = [g | u] [M, 2F]: the per-token
+// activation codes of the W8A8 down projection (gemm_w8a8.hip).  h is recomputed from gu in the encode
+// pass (the row's second read comes from L2) and never written: the bytes of quant_w8_rows(swiglu_fwd(gu)).
+__global__ __launch_bounds__(256) void swiglu_quant_w8_rows_k(const bf16* __restrict__ GU, long long ldg,
+                                                               uint8_t* __restrict__ codes, long long ldc,
+                                                               float* __restrict__ inv, int F) {
+  __shared__ float red[4];
+  const long long m = blockIdx.x;
+  const bf16* gr = GU + m * ldg;
+  const int nv = F / 8;
+  float a = 0.f;
+  for (int j = threadIdx.x; j < nv; j += 256) a = kv8_amax8(swiglu8_w8(gr + 8 * j, gr + F + 8 * j), a);
+  a = wave_max(a);
+  if (lane_id() == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  const float scale = kv8_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+  for (int j = threadIdx.x; j < nv; j += 256)
+    *reinterpret_cast<u32x2*>(codes + m * ldc + 8 * j) = kv8_enc8(swiglu8_w8(gr + 8 * j, gr + F + 8 * j), scale);
+  if (threadIdx.x == 0) inv[m] = 1.f / scale;
+}
 
 // codes 8h .. 8h + 7 of a 16-code load (words 2h, 2h + 1) -> 8 bf16, exact
 __device__ __forceinline__ bf16x8 w8_cvt8(uint32_t w0, uint32_t w1) {
@@ -207,4 +239,11 @@ extern "C" void dpfs_gemv_w8(const void* A, long long lda, const void* codes, lo
 extern "C" void dpfs_quant_w8_rows(const void* W, long long ldw, void* codes, long long ldc, float* inv, int N, int K,
                                    hipStream_t s) {
   if (N > 0) quant_w8_rows_k<<<N, 256, 0, s>>>((const bf16*)W, ldw, (uint8_t*)codes, ldc, inv, K);
+}
+
+// gu bf16 [M, 2F] = [gate | up] (row stride ldg elements, ldg % 8 == 0, F % 8 == 0, 16-byte aligned) ->
+// codes uint8 [M, F] (row stride ldc bytes, ldc % 8 == 0) and inv fp32 [M] of the rows bf16(silu(gate) * up).
+extern "C" void dpfs_swiglu_quant_w8_rows(const void* gu, long long ldg, void* codes, long long ldc, float* inv, int M,
+                                          int F, hipStream_t s) {
+  if (M > 0) swiglu_quant_w8_rows_k<<<M, 256, 0, s>>>((const bf16*)gu, ldg, (uint8_t*)codes, ldc, inv, F);
 }

@@ -100,6 +100,10 @@ def get_test_args(argv=None):
     g.add_argument("--quantised_prefill", action="store_true",
                    help="with --weight_dtype fp8 / mxfp4: the prefill and every extend piece on the weight codes "
                         "too (one model for the prompt and the generated tokens), and no batch cap of 64")
+    g.add_argument("--prefill_act_dtype", choices=["act", "fp8"], default="act",
+                   help="with --quantised_prefill --weight_dtype fp8: fp8 also rounds the activations of the "
+                        "projections above 64 rows to e4m3, one scale per token and no calibration (W8A8 on the "
+                        "fp8 MFMA; changes accuracy)")
     g.add_argument("--kv_page", type=int, default=0,
                    help="keep the KV cache in pages of this many tokens (a power of two in [16, 256]; 0: contiguous)")
     g.add_argument("--kv_pool_pages", type=int, default=0,
@@ -281,7 +285,7 @@ def test(rank, args):
     if args.weight_dtype != "act":
         sampling["weight_dtype"] = args.weight_dtype
     if args.quantised_prefill:
-        sampling["quantised_prefill"] = True
+        sampling["quantised_prefill"] = "a8" if args.prefill_act_dtype == "fp8" else True
     pens = dict(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
                 frequency_penalty=args.frequency_penalty)
     if pens != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
@@ -355,6 +359,9 @@ def main(argv=None):
         raise ValueError("--weight_dtype chooses the weights of the KV-cached decode steps: drop --no_kv_cache")
     if args.quantised_prefill and args.weight_dtype == "act":
         raise ValueError("--quantised_prefill runs the prefill on the weight codes: give --weight_dtype fp8 or mxfp4")
+    if args.prefill_act_dtype == "fp8" and not (args.quantised_prefill and args.weight_dtype == "fp8"):
+        raise ValueError("--prefill_act_dtype fp8 rounds the activations of the quantised prefill to e4m3: give "
+                         "--quantised_prefill --weight_dtype fp8")
     check_kv_page_args(args)
     import torch.multiprocessing as mp
     os.environ.setdefault("MASTER_ADDR", args.master_addr)

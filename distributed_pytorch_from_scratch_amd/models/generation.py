@@ -75,6 +75,12 @@ kernels and order of ``decode_step`` on B*T rows with the attention part of the 
 MFMA GEMM on codes (``_gemm_nt_w8`` / ``_gemm_nt_w4``, csrc/kernels/gemm_wq.hip), those of up to 64 rows
 on the decode kernels (``_projector``).
 
+W8A8 prefill (``quantised_prefill="a8"`` with ``weight_dtype="fp8"``; ``cache.wq_prefill == "a8"``, a session
+key element of its own): the projections of more than 64 rows also round their activation rows to e4m3,
+one fp32 scale per token (``_quant_w8_rows`` on the rows; ``_swiglu_quant_w8_rows`` for the down
+projection), and run on the fp8 MFMA (``_gemm_nt_w8a8``, csrc/kernels/gemm_w8a8.hip).  No calibration and
+no outlier handling: an accuracy change the caller opts into.  Rows up to 64 keep ``_gemv_nt_w8``.
+
 ``generate(model, prompt, ...)`` returns the prompt followed by the generated ids.
 ``logits_step`` exposes the last-position logits (tests compare it against the full recompute).
 """
@@ -110,6 +116,7 @@ class KVCache:
     w8 = None   # fp8 decode weights of the session (``quantise_weights``); None: bf16 weights
     w4 = None   # MXFP4 decode weights of the session (``quantise_weights``); None: bf16 or fp8 weights
     wq_prefill = False   # ``quantised_prefill``: every projection of the session on its codes, at any row count
+    #                      ("a8": those of more than 64 rows on per-token e4m3 activation codes too)
 
     def __init__(self, n_layers: int, B: int, t_max: int, h_local: int, hd: int, dtype, device,
                  ragged: bool = False, kv_dtype: Optional[str] = None):
@@ -367,9 +374,12 @@ WEIGHT_DTYPES = {"fp8": 64, "mxfp4": 128}     # weight_dtype -> the K multiple i
 def _check_weight_dtype(model, B: int, weight_dtype, who: str = "generate", quantised_prefill: bool = False) -> None:
     if weight_dtype is None:
         if quantised_prefill:
-            raise ValueError(f"{who}: quantised_prefill=True needs a weight_dtype ('fp8' or 'mxfp4'): it runs the "
-                             "prefill on the session's weight codes")
+            raise ValueError(f"{who}: quantised_prefill={quantised_prefill!r} needs a weight_dtype ('fp8' or 'mxfp4'): it "
+                             "runs the prefill on the session's weight codes")
         return
+    if quantised_prefill == "a8" and weight_dtype != "fp8":
+        raise ValueError(f"{who}: quantised_prefill='a8' needs weight_dtype='fp8' (e4m3 activations meet e4m3 weight "
+                         f"codes on the fp8 MFMA), got {weight_dtype!r}")
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"{who}: weight_dtype must be None (the activation dtype), 'fp8' or 'mxfp4', got "
                          f"{weight_dtype!r}")
@@ -491,9 +501,14 @@ def _projector(cache: KVCache, k, dt, rows: int):
     whose rounding is the fused operand's).  A projection without codes (K % 64 != 0) or whose operands
     the kernel declines (a pinned library backend) keeps the bf16 route; with d, the local head width
     and the local ffn width all multiples of 64 no projection falls back.  MXFP4 weights (cache.w4): the
-    same on gemv_w4_k / gemm_wq_k, with 128 for 64."""
+    same on gemv_w4_k / gemm_wq_k, with 128 for 64.
+
+    ``quantised_prefill="a8"`` (``cache.wq_prefill == "a8"``, fp8 weights): a projection of more than 64 rows
+    first takes ``GS.big_nt_w8a8`` (the rows quantised per token, SwiGLU inside that quantiser instead of a
+    ``swiglu_fwd`` pass, then gemm_w8a8_k on the fp8 MFMA); one it declines (K % 128 != 0) takes gemm_wq_k."""
     small = rows <= 16
     big = cache.wq_prefill and rows > W8_MAX_BATCH
+    a8 = big and cache.wq_prefill == "a8"
     if cache.w4 is not None:
         wq, small_q, big_q = cache.w4, GS.small_nt_w4, GS.big_nt_w4
     else:
@@ -501,6 +516,10 @@ def _projector(cache: KVCache, k, dt, rows: int):
 
     def proj(a, w, bias=None, swiglu=False):
         q = wq.get(id(w))
+        if q is not None and a8:
+            y = GS.big_nt_w8a8(k, a, q, bias, swiglu)
+            if y is not None:
+                return y
         if q is not None and big:
             a, swiglu = (k.swiglu_fwd(a) if swiglu else a), False
             y = big_q(k, a, q, bias)
@@ -980,7 +999,8 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
     if kv_page:
         key += (kv_page, kv_pool_pages)
     if weight_dtype:
-        key += (("weights", weight_dtype) + (("prefill",) if quantised_prefill else ()),)
+        key += (("weights", weight_dtype) + (("prefill",) if quantised_prefill else ()) +
+                (("a8",) if quantised_prefill == "a8" else ()),)
     vers = tuple(p._version for p in model.parameters())
     ent = _SESSIONS.get(key)
     if ent is not None and ent["model"]() is model and ent["vers"] == vers:
@@ -996,7 +1016,7 @@ def _session(model, B: int, t_max: int, dev, ragged: bool = False, kv_dtype: Opt
         cache.w8 = quantise_weights(model, dev)
     elif weight_dtype == "mxfp4":
         cache.w4 = quantise_weights(model, dev, "mxfp4")
-    cache.wq_prefill = bool(weight_dtype and quantised_prefill)
+    cache.wq_prefill = "a8" if quantised_prefill == "a8" else bool(weight_dtype and quantised_prefill)
     graphs = {}
     kv_bytes = cache.nbytes()             # the fp8 form: codes and scales; the paged form: pools and table
     keep_gb = float(os.environ.get("DPFS_DECODE_SESSION_MAX_GB", "16"))
@@ -1124,7 +1144,10 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, eos_id: Optional[
     last rows' lm_head likewise; and the batch cap of 64 is lifted, decode steps of more rows take the
     tiled kernel.  A weight without codes keeps its bf16 route as above.  The bf16 weights stay loaded
     (the embedding, the norms and the biases are read from the model as ever).  ``False``, the default,
-    changes nothing."""
+    changes nothing.  ``"a8"`` (``weight_dtype="fp8"`` only; ``ValueError`` with ``"mxfp4"`` or none) is ``True``
+    with the activations of every projection above 64 rows rounded to e4m3 as well, one fp32 scale per token
+    row and no calibration, on the fp8 MFMA GEMM (``_gemm_nt_w8a8``, csrc/kernels/gemm_w8a8.hip): W8A8, a
+    visible accuracy change, hence its own value."""
     _check_weight_dtype(model, prompt.size(0), weight_dtype, quantised_prefill=quantised_prefill)
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate: kv_dtype must be None (the activation dtype) or 'fp8', got {kv_dtype!r}")

@@ -106,6 +106,10 @@ def _gemm_nt_w4_ok(x, codes) -> bool:
     return False
 
 
+def _gemm_nt_w8a8_ok(xc, codes) -> bool:
+    return False     # fp8 activations on fp8 weights: a bf16-compute session's route
+
+
 # single-token decode (models/generation.py): bf16 kernels only; fp32 decode on tensor ops
 # (the token choice, sample_logits / _sample_logits_rows / _sample_logits_pen, takes fp32 rows
 # too and reaches the kernel through __getattr__ below)

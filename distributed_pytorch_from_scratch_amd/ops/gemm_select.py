@@ -354,6 +354,22 @@ def big_nt_w8(k, x: torch.Tensor, w8, bias=None) -> Optional[torch.Tensor]:
     return None
 
 
+def big_nt_w8a8(k, x: torch.Tensor, w8, bias=None, swiglu: bool = False) -> Optional[torch.Tensor]:
+    """``big_nt_w8`` with the activation rows rounded to e4m3 too (W8A8): the rows of ``x``, or with ``swiglu``
+    of silu(gate) * up of the packed x = [gate | up], get one fp32 scale per token (``_quant_w8_rows`` /
+    ``_swiglu_quant_w8_rows``: one launch), then y = (xc codes^T) * sa[m] * inv[n] (+ bias) on gemm_w8a8_k
+    (csrc/kernels/gemm_w8a8.hip: the fp8 MFMA on both code matrices, no conversion).  None where the kernel
+    does not take the shape (K % 128, strides) or the library backend is pinned: the caller keeps
+    ``big_nt_w8`` for that projection."""
+    codes, inv = w8
+    if not (_direct(k) or not x.is_cuda):
+        # the activation codes come out contiguous [M, K], so the weight codes decide (a row of them stands in)
+        if mode() == "blas" or x.stride(1) != 1 or x.stride(0) % 8 or not k._gemm_nt_w8a8_ok(codes[:1], codes):
+            return None
+    xc, sa = k._swiglu_quant_w8_rows(x) if swiglu else k._quant_w8_rows(x)
+    return k._gemm_nt_w8a8(xc, sa, codes, inv, bias).to(x.dtype)       # (bf16; the fp32 oracle path widens it)
+
+
 def big_nt_w4(k, x: torch.Tensor, w4, bias=None) -> Optional[torch.Tensor]:
     """``big_nt_w8`` on MXFP4 weights: ``w4`` as in ``small_nt_w4``; y = x wq^T (+ bias), K % 128."""
     codes, scales = w4

@@ -555,6 +555,28 @@ def _gemm_nt_w8(x: torch.Tensor, codes: torch.Tensor, inv: torch.Tensor,
     return _gemv_nt_w8(x, codes, inv, bias)
 
 
+def _gemm_nt_w8a8_ok(xc: torch.Tensor, codes: torch.Tensor) -> bool:
+    return True
+
+
+def _gemm_nt_w8a8(xc: torch.Tensor, sa: torch.Tensor, codes: torch.Tensor, inv: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W8A8: y = bf16((f32(xc) f32(codes)^T) * sa[m] * inv[n] (+ bias)) on e4m3 activation codes ``xc``
+    uint8 [M, K] with one fp32 scale per token row ``sa`` [M] (the rows of ``_quant_w8_rows`` of the
+    activations) and the weight codes of ``_gemv_nt_w8``; fp32 on the codes, both scales applied once to the
+    finished sum (the GPU's fp8 MFMA kernel, csrc/kernels/gemm_w8a8.hip)."""
+    y = (xc.view(torch.float8_e4m3fn).float() @ codes.view(torch.float8_e4m3fn).float().t()) * sa[:, None] * inv
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(torch.bfloat16)
+
+
+def _swiglu_quant_w8_rows(gu: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``_quant_w8_rows(swiglu_fwd(gu))`` of a packed gu = [g | u] [M, 2F]: the per-token codes and scales
+    of the W8A8 down projection's operand (one GPU kernel, the F-wide activation never written)."""
+    return _quant_w8_rows(swiglu_fwd(gu))
+
+
 def _gemm_nt_w4_ok(x: torch.Tensor, codes: torch.Tensor) -> bool:
     return True
 

@@ -66,7 +66,10 @@ route (M > 16), 100 launches per graph replay, with weight bytes / time (``w8_ke
 codes, with ``quantised_prefill`` off (the prefill on bf16 weights) and on (every projection on codes), in
 the same interleaved rounds.  ``--wq-kernel`` times the quantised-weight GEMM launch alone
 (``_gemm_nt_w8`` / ``_gemm_nt_w4``, csrc/kernels/gemm_wq.hip) against ``gemm_nt`` on the bf16 weight, on the
-preset's projection shapes at every ``--batch`` M (``wq_kernel_bench``).
+preset's projection shapes at every ``--batch`` M (``wq_kernel_bench``).  Where K % 128 == 0 the same rounds
+also time the W8A8 route of ``quantised_prefill="a8"``: the per-token quantiser (``_quant_w8_rows`` on the rows;
+``_swiglu_quant_w8_rows`` for the down projection), ``_gemm_nt_w8a8`` (csrc/kernels/gemm_w8a8.hip) and both
+together; every line carries the rounds' median, min and max.
 
 ``--continuation --extend-split 0 auto N ...`` times the extend-attention launch alone, unsplit against the
 split form (``_attn_extend_split``) at the rule's and at forced split counts, over short chunks and long
@@ -460,8 +463,8 @@ def w8_kernel_bench(a, args):
 
 
 def wq_kernel_bench(a, args):
-    """``--wq-kernel``: us per launch of ``_gemm_nt_w8`` / ``_gemm_nt_w4`` and of ``gemm_nt`` on the bf16
-    weight, on the preset's projection shapes at every ``--batch`` M, 20 launches per timed window, in
+    """``--wq-kernel``: us per launch of ``_gemm_nt_w8`` / ``_gemm_nt_w4``, of the W8A8 route (``a8_quant``: the
+    per-token quantiser, ``a8_gemm``: ``_gemm_nt_w8a8``, ``a8``: both) and of ``gemm_nt`` on the bf16 weight, on the preset's projection shapes at every ``--batch`` M, 20 launches per timed window, in
     interleaved rounds; one JSON line per (projection, M, kernel)."""
     import torch
     from distributed_pytorch_from_scratch_amd.ops import _ext
@@ -475,6 +478,13 @@ def wq_kernel_bench(a, args):
             launch = {"gemm_nt": lambda: C.gemm_nt(x, w), "w8": lambda: C._gemm_nt_w8(x, *q8)}
             if q4:
                 launch["w4"] = lambda: C._gemm_nt_w4(x, *q4)
+            if K % 128 == 0:      # W8A8: the per-token quantiser (the fused SwiGLU one for down), the fp8 MFMA GEMM, both
+                src = torch.randn(M, 2 * K, device="cuda").bfloat16() if name == "down" else x
+                quant = C._swiglu_quant_w8_rows if name == "down" else C._quant_w8_rows
+                xc, sa = quant(src)
+                launch["a8_quant"] = lambda: quant(src)
+                launch["a8_gemm"] = lambda: C._gemm_nt_w8a8(xc, sa, *q8)
+                launch["a8"] = lambda: C._gemm_nt_w8a8(*quant(src), *q8)
             us = {k_: [] for k_ in launch}
             for fn in launch.values():
                 fn()
@@ -491,6 +501,7 @@ def wq_kernel_bench(a, args):
                 med = _median(us[k_])
                 print(json.dumps({"bench": "wq_kernel", "model": a.model, "proj": name, "M": M, "N": N, "K": K,
                                   "kernel": k_, "us_per_call": us[k_], "us_per_call_median": med,
+                                  "us_per_call_min": min(us[k_]), "us_per_call_max": max(us[k_]),
                                   "tflops": round(2e-6 * M * N * K / med, 1),
                                   "vs_gemm_nt": round(med / _median(us["gemm_nt"]), 3)}), flush=True)
 
